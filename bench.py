@@ -13,9 +13,14 @@ N > 1 runs either as one process per GPU under torch.distributed.run (backend nc
 as ONE process that drives all N devices through the library's own multi-device entry (mcgpu_multi_run_thermal:
 RCCL inside the library, the entry a single-process Fortran host binds); the line says which ("launcher").
 
-On one GPU the same line carries a block per BASELINE configuration that fits one GPU -- ref4.1 2D (configs[1]),
-ref4.1_3D, the Voronoi stand-in, ref4.1 with 10x the dust + MRW, the SED-mode Monte Carlo with 10 observers -- each
-with its own roofline, CPU baseline and temperature parity (`--no-extra` leaves them out, `--config X` runs one alone).
+A plain run measures the headline alone: set-up, W warm-up steps, K timed steps, the line.  With `--full` it also runs
+the CPU baseline and the temperature parity against it, and on one GPU the same line carries a block per BASELINE
+configuration that fits one GPU -- ref4.1 2D (configs[1]), ref4.1_3D, the Voronoi stand-in, ref4.1 with 10x the dust +
+MRW, the SED-mode Monte Carlo with 10 observers -- each with its own roofline, CPU baseline and temperature parity
+(`--no-extra` leaves them out, `--config X` runs one alone).
+
+`--dump-outputs DIR` writes what the timed path returned in its last step (rank 0: E_abs, sed, n_sent, counters) as
+DIR/<name>.npy in float64, so that two builds can be compared output for output: the seeds depend on the step only.
 """
 import argparse
 import json
@@ -86,6 +91,25 @@ def pmc_summary(config, n_local, world):
         return out
     except Exception:
         return {}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Writes `arrays` as path/<name>.npy in float64.  An array larger than its share of DUMP_LIMIT_BYTES is written as a
+    fixed sample (the same flat indices in every run: seed 0, sorted), with the indices next to it as <name>_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (2 * max(1, len(arrays)))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            a = a.ravel()
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 16, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(model, n_total, target_s=15.0):
@@ -258,9 +282,10 @@ def build_workload(M, args, config):
     return cfg, model
 
 
-def thermal_block(par, args, config, steps, warmup, with_cpu, n_local, crossing=None):
-    """Times `steps` passes of the thermal packet loop on one configuration; returns (block or None on ranks > 0, cfg)."""
-    from mcfost_amd.engine import Engine, MultiEngine
+def thermal_block(par, args, config, steps, warmup, with_cpu, n_local, crossing=None, dump=None):
+    """Times `steps` passes of the thermal packet loop on one configuration; returns (block or None on ranks > 0, cfg).
+    `dump`: a directory for the last step's outputs (dump_outputs)."""
+    from mcfost_amd.engine import COUNTER_NAMES, Engine, MultiEngine
     from mcfost_amd.host import model as M
     cfg, model = build_workload(M, args, config)
     world = par.n_gpus
@@ -313,6 +338,9 @@ def thermal_block(par, args, config, steps, warmup, with_cpu, n_local, crossing=
     if me is not None:
         par.rccl_ranks = me.rccl_ranks()
     cnt = out["counters"]
+    if dump and par.rank == 0:
+        dump_outputs(dump, {"E_abs": out["E_abs"], "sed": out["sed"], "n_sent": out["n_sent"],
+                            "counters": [cnt[k] for k in COUNTER_NAMES]})
     block = None
     if par.rank == 0:
         cross_pp = cnt["crossings"] / max(cnt["packets"], 1)
@@ -384,7 +412,7 @@ def thermal_block(par, args, config, steps, warmup, with_cpu, n_local, crossing=
         if block["tail"]["host_events"]:
             block["tail"]["host_ns_per_event_per_thread"] = (block["tail"]["host_ms"] * 1e6 * block["tail"]["host_threads"] /
                                                             block["tail"]["host_events"])
-        if config == "voronoi" and me is None:
+        if config == "voronoi" and me is None and args.full:
             # The crossing engine alone: the same grid, the same kernel, the same packets, but a transparent disk
             # (kappa_factor = 0: no interaction ever) -- crossings per second without the 119 interactions per packet of the
             # stand-in disk that share the step with them; and the step's split that rate implies.
@@ -475,12 +503,13 @@ def thermal_block(par, args, config, steps, warmup, with_cpu, n_local, crossing=
     return block, cfg
 
 
-def sed_block(par, args, steps, warmup, with_cpu, packets, observers, all_lambdas=False, n2=None):
+def sed_block(par, args, steps, warmup, with_cpu, packets, observers, all_lambdas=False, n2=None, dump=None):
     """SED mode on the ref4.1 grid (the second half of BASELINE config 2): one step = the SED Monte Carlo
     (mcgpu_run_mono: scout + commit passes, ray-tracing deposits) of the listed wavelengths, every stream asked for
-    packets/128/len(wavelengths) packets in the stop bin; streams sharded over the GPUs."""
+    packets/128/len(wavelengths) packets in the stop bin; streams sharded over the GPUs.  `dump`: a directory for the last
+    step's outputs, per wavelength (dump_outputs)."""
     from mcfost_amd import distributed as D
-    from mcfost_amd.engine import Engine, MultiEngine
+    from mcfost_amd.engine import COUNTER_NAMES, Engine, MultiEngine
     from mcfost_amd.host import model as M
 
     world = par.n_gpus
@@ -516,6 +545,7 @@ def sed_block(par, args, steps, warmup, with_cpu, packets, observers, all_lambda
 
     xlog_tot = {"launches": 0.0, "records": 0.0, "flights": 0.0}
     ev_tot = {"packets": 0.0, "crossings": 0.0}     # the step's commit passes, every wavelength (rank 0's streams)
+    last = {}                                        # the step's result per wavelength (the last step's after the loop)
 
     def step(i):
         sent = 0
@@ -531,6 +561,7 @@ def sed_block(par, args, steps, warmup, with_cpu, packets, observers, all_lambda
                 td = eng.repartition_energie(lam, T, fetch=False)
                 r = eng.run_mono(lam, n2, seed=100 + i, n_chunks=count, first_chunk=first, fetch_xI=False, device_tables=td,
                                  block_threads=args.block_threads)
+            last[lam] = r
             sent += int(r["n_sent_chunk"].sum())
             for k in ev_tot:        # (a wavelength's run starts its counters at zero)
                 ev_tot[k] += float(r["counters"][k])
@@ -553,6 +584,13 @@ def sed_block(par, args, steps, warmup, with_cpu, packets, observers, all_lambda
     par.barrier()
     dt = par.max_over_ranks(time.perf_counter() - t0)
     sent_all = par.sum_over_ranks(float(sent))
+    if dump and par.rank == 0:
+        arrays = {}
+        for lam, r in last.items():
+            for k in ("sed", "n_sent", "n_sent_chunk"):
+                arrays["%s_lambda%d" % (k, lam)] = r[k]
+            arrays["counters_lambda%d" % lam] = [r["counters"][k] for k in COUNTER_NAMES]
+        dump_outputs(dump, arrays)
     block = None
     if par.rank == 0:
         if me is not None:
@@ -628,7 +666,13 @@ def main():
                          "sph: the analytic density at the site, m (1.2 / h)^3 (what a dump's own SPH density would be): at 1e6 "
                          "sites the few cells of the inner rim then carry its midplane density through their whole depth, "
                          "1300 crossings + 1250 interactions per packet (profiles/r04_voronoi_sph_density.json)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline and the temperature parity against it, the other BASELINE "
+                         "configurations as blocks of the same line (--config pascucci, one GPU), the Voronoi crossing engine "
+                         "alone.  Off: the run times the headline steps and prints the line, nothing else")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline (and the parity) out")
     ap.add_argument("--sed-observers", type=int, default=0, help="--config sed: RT_n_incl (default: the configuration's)")
     ap.add_argument("--xI-precision", type=int, default=4, choices=[4, 8],
                     help="--config sed: mcgpu_set_xI_precision -- 4 (default here): xI_scatt accumulated in default real, the type of "
@@ -641,10 +685,10 @@ def main():
                     "interactions in a row in one cell (dust_transfer.f90:1223: 5; 0..6)")
     ap.add_argument("--dust-mass", type=float, default=0.0, help="override the disk's dust mass [Msun] (thermal configs; "
                     "ref41_mrw defaults to 10x the stock mass)")
-    ap.add_argument("--no-ref41", action="store_true", help="--config pascucci: the headline block alone (same as --no-extra)")
-    ap.add_argument("--no-extra", action="store_true", help="--config pascucci: the headline block alone")
+    ap.add_argument("--no-ref41", action="store_true", help="--full, --config pascucci: the headline block alone (same as --no-extra)")
+    ap.add_argument("--no-extra", action="store_true", help="--full, --config pascucci: the headline block alone")
     ap.add_argument("--no-pascucci", action="store_true", help="(kept for older command lines: same as --no-extra)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0)
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="--full: the CPU baseline's target time [s]")
     ap.add_argument("--shared-device", action="store_true",
                     help="--gpus N started plainly (library mode) on a box with ONE GPU: the N contexts share device 0 and the "
                          "library's own sum stands in for the RCCL all-reduce -- a dry run of the multi-device code, not a "
@@ -678,14 +722,14 @@ def main():
     if par.mode == "torchrun" and par.world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE = %d" % (args.gpus, par.world))
     world = par.n_gpus
-    with_cpu = world == 1 and not args.no_cpu_baseline
+    with_cpu = args.full and world == 1 and not args.no_cpu_baseline
     launcher = {"single": "one process, one GPU", "torchrun": "one process per GPU, torch.distributed nccl (RCCL)",
                 "library": "one process, mcgpu_multi_* (RCCL inside the library)"}[par.mode]
     if par.mode == "library" and par.shared_device:
         launcher = "one process, mcgpu_multi_* with every context on device 0 (shared-device dry run: NOT a scaling measurement)"
 
     if args.config == "sed":
-        line = sed_block(par, args, args.steps, args.warmup, with_cpu, args.packets, args.sed_observers)
+        line = sed_block(par, args, args.steps, args.warmup, with_cpu, args.packets, args.sed_observers, dump=args.dump_outputs)
         if par.rank == 0:
             line["launcher"] = launcher
             if par.rccl_ranks is not None:
@@ -700,10 +744,10 @@ def main():
         if par.rank == 0 and blk is not None:
             print("block %s: %s" % (name, json.dumps(blk)), flush=True)
 
-    block, cfg = thermal_block(par, args, args.config, args.steps, args.warmup, with_cpu, args.packets)
+    block, cfg = thermal_block(par, args, args.config, args.steps, args.warmup, with_cpu, args.packets, dump=args.dump_outputs)
     say("headline_" + args.config, block)
     extras = {}
-    if args.config == "pascucci" and not (args.no_ref41 or args.no_pascucci or args.no_extra) and not args.frozen:
+    if args.full and args.config == "pascucci" and not (args.no_ref41 or args.no_pascucci or args.no_extra) and not args.frozen:
         # BASELINE.json lists ref4.1 as the single-GPU configuration (configs[1]): the same loop, same packet count,
         # same steps, barriers and all-reduce, with its own roofline, CPU baseline and temperature parity
         extras["ref41_2d"], _ = thermal_block(par, args, "ref41", args.steps, args.warmup, with_cpu, args.packets)

@@ -118,3 +118,62 @@ def test_more_gpus_than_the_node_has_is_an_error_not_a_number():
                          env=env, cwd=root)
     assert out.returncode != 0 and "--gpus 64" in out.stderr and "GPU(s)" in out.stderr
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_outputs_writes_float64_within_the_size_limit(tmp_path):
+    """`bench.py --dump-outputs DIR`: every array as DIR/<name>.npy in float64; one larger than its share of the 64 MB
+    is written as a fixed sample with its flat indices, the same in every run."""
+    import bench
+    big = np.arange(20_000_000, dtype=np.float64)          # 160 MB
+    small = {"E_abs": np.linspace(0.0, 1.0, 7000), "counters": [3, 2**40 + 1, 0]}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), dict(small, big=big))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["E_abs.npy", "big.npy", "big_index.npy", "counters.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    assert np.array_equal(np.load(tmp_path / "a" / "E_abs.npy"), small["E_abs"])
+    assert np.load(tmp_path / "a" / "counters.npy").tolist() == [3.0, 2.0**40 + 1, 0.0]
+    idx = np.load(tmp_path / "a" / "big_index.npy")
+    assert np.all(np.diff(idx) > 0) and np.array_equal(np.load(tmp_path / "a" / "big.npy"), big[idx.astype(np.int64)])
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_plain_run_times_the_headline_alone(monkeypatch, capsys, full):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs the headline block alone, without the CPU baseline; with
+    --full it also runs the CPU baseline and every other configuration's block, as a plain run did before --full."""
+    import json
+    import sys
+    import types
+    import bench
+    calls = []
+
+    def thermal_block(par, args, config, steps, warmup, with_cpu, n_local, crossing=None, dump=None):
+        calls.append(("thermal", config, steps, warmup, with_cpu, crossing, dump))
+        blk = {"value": 1.0, "unit": "packets/s", "ms_per_step": 2.0, "config": {}, "roofline": {"kernel": "k"},
+               "tail": {}}
+        return blk, types.SimpleNamespace(name="Pascucci")
+
+    def sed_block(par, args, steps, warmup, with_cpu, packets, observers, all_lambdas=False, n2=None, dump=None):
+        calls.append(("sed", steps, warmup, with_cpu, dump))
+        return {"value": 1.0}
+
+    monkeypatch.setattr(bench, "thermal_block", thermal_block)
+    monkeypatch.setattr(bench, "sed_block", sed_block)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "d"] + (["--full"] if full else [])
+    monkeypatch.setattr(sys, "argv", argv)
+    bench.main()
+    line = json.loads([l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1])
+    assert calls[0] == ("thermal", "pascucci", 7, 2, full, None, "d")
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] == 2.0
+    assert all(line[k] is not None for k in ("metric", "value", "unit", "higher_is_better", "dtype"))
+    if not full:
+        assert len(calls) == 1 and "ref41_2d" not in line and "sed" not in line
+    else:
+        assert {c[1] for c in calls if c[0] == "thermal"} == {"pascucci", "ref41", "ref41_3d", "voronoi", "ref41_mrw"}
+        assert any(c[0] == "sed" for c in calls) and all(c[-1] is None for c in calls[1:])
+        assert {"ref41_2d", "ref41_3d", "voronoi", "ref41_mrw", "sed", "pascucci_parametric_crossing"} <= set(line)
