@@ -285,10 +285,15 @@ __device__ inline int roles_cross(const Lds& T, const DevModel& M, const RunArgs
 // Every value that decides an index or a position is computed by the reference's expression, exactly as in
 // cross_cell_lean / roles_cross above (cylindrical_grid.f90:918-1175, optical_depth.f90:77-178).
 // OUT: the deposit is handed back (dep_ic >= 0, dep_v) instead of being made (the tail kernel, mc_tail.hip.h)
-template <bool DARK, bool LDSE, bool MRW = false, bool OUT = false, bool VAR = false>
+// WAVE: the flying waves' loop of the role kernel, whose bookkeeping goes per visit instead of per crossing (as in
+// fly_step_2d_param): c_cross counts the WAVE's crossings (a ballot and a scalar add; the caller adds them to one lane's
+// counter), the star's cell is tested only when any_star says some lane of the wave flies towards one, and the caller
+// counts the packets killed there and tests the packet's crossing counter for a runaway, once per visit.  Positions,
+// indices, deposits: the same bits.
+template <bool DARK, bool LDSE, bool MRW = false, bool OUT = false, bool VAR = false, bool WAVE = false>
 __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, const RunArgs& A, double* E_lds, Flight& p,
                                            unsigned int& c_cross, unsigned int& c_kill, unsigned int& c_dark,
-                                           int* dep_ic = nullptr, double* dep_v = nullptr) {
+                                           int* dep_ic = nullptr, double* dep_v = nullptr, bool any_star = true) {
   const int n_rad = M.n_rad, nz = M.nz;
   // correct_plus = 1 + e and correct_moins = 1 - e with e = 45 * 2^-52 EXACTLY (1e-14 rounds to 45 units in the last
   // place of 1.0 and 90 of the doubles below it): a * correct_plus = a + a e is then one fma(a, e, a) -- the very
@@ -300,8 +305,10 @@ __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, cons
   const double x0 = p.x, y0 = p.y, z0 = p.z, u = p.u, v = p.v, w = p.w;
   const bool top = (zj0 == nz + 1);
   // test_exit_grid_cyl (cylindrical_grid.f90:680-704) in closed form; the star's cell (optical_depth.f90:91-97)
-  const bool out = (ri0 == n_rad + 1) || (top && (fabs(z0) > M.zmaxmax));
-  const bool killed = (p.star_key >= 0) && (ri0 + (n_rad + 2) * (zj0 + nz + 1) == p.star_key);
+  // (bitwise: compares and mask operations, no short-circuit)
+  const bool out = (ri0 == n_rad + 1) | (top & (fabs(z0) > M.zmaxmax));
+  bool killed = false;
+  if (!WAVE || any_star) killed = (p.star_key >= 0) & (ri0 + (n_rad + 2) * (zj0 + nz + 1) == p.star_key);
   const bool go = active && !out && !killed;
   const bool hole = (ri0 == 0);
   // the cell's index travels with the flight (p.ic; n_cells = "no cell"): what the last crossing computed for the
@@ -332,9 +339,12 @@ __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, cons
   const double dz = w * z0;
   const bool away = dz > 0.0;
   const bool flip = !away && (zj0 == 1);  // through the midplane to the mirror side
-  const int jsel = away ? zj0 + 1 : (zj0 == 1 ? 2 : zj0);
+  const int jm = away ? zj0 : (zj0 == 1 ? 1 : zj0 - 1);   // jsel - 1, jsel = away ? zj0 + 1 : (zj0 == 1 ? 2 : zj0)
   // (jsel = nz + 2, where z_lim is 1e30, only occurs for away && top, which the 1e10 below replaces)
-  double zmag = (jsel <= nz) ? ((double)jsel - 1.0) * R0.ch : R0.zmax;
+  // (jsel - 1) ch for jsel <= nz, else zmax: ONE read of the row at the offset that applies, times (double)(jsel - 1)
+  // = (double)jsel - 1.0 or 1.0 (both exact) -- the same product, or zmax itself, without a divergent branch
+  const bool below = jm < nz;
+  double zmag = (double)(below ? jm : 1) * *(below ? &R0.ch : &R0.zmax);
   // zmag * (away ? correct_plus : correct_moins), see the top of the function
   zmag = __builtin_fma(zmag, __longlong_as_double(away ? 0x3D06800000000000ll : (long long)0xBD06800000000000ull), zmag);
   zmag = (away && top) ? 1.0e10 : zmag;
@@ -387,7 +397,8 @@ __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, cons
   }
 
   // the next cell; DARK: mirrored back at the wall of a dark cell (see roles_cross)
-  const bool next_real = (ri1 >= 1) && (ri1 <= n_rad) && (zj1 >= 1) && (zj1 <= nz);
+  // (unsigned compares: 1 <= ri1 <= n_rad and 1 <= zj1 <= nz in one test each)
+  const bool next_real = ((unsigned)(ri1 - 1) < (unsigned)n_rad) & ((unsigned)(zj1 - 1) < (unsigned)nz);
   const int ic1 = next_real ? (ri1 - 1) + n_rad * (zj1 - 1) : M.n_cells;  // (n_cells: the entry of "no cell", 0)
   bool mirror = false;
   if (DARK) mirror = go && !stop && next_real && M.dark[next_real ? ic1 : 0];
@@ -418,11 +429,17 @@ __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, cons
   st = (active && out) ? S_EXITED : st;
   st = (active && !out && killed) ? S_EMIT : st;
   st = (stop || mirror) ? S_INTERACT : st;
-  c_cross += go ? 1u : 0u;
-  c_kill += (active && !out && killed) ? 1u : 0u;
   p.pk_cross += go ? 1u : 0u;
   // MRW: bit 31 of the crossing counter remembers that this flight has left the cell it started in
   if (MRW) p.pk_cross |= (move || mirror) ? 0x80000000u : 0u;
+  if (WAVE) {  // (a packet killed at the star's cell is the only one a crossing turns from S_FLIGHT into S_EMIT here: the
+               // caller counts those once per visit)
+    c_cross += (unsigned int)__popcll(__ballot(go));
+    p.st = st;
+    return 0;
+  }
+  c_cross += go ? 1u : 0u;
+  c_kill += (active && !out && killed) ? 1u : 0u;
   const bool runaway = go && ((MRW ? (p.pk_cross & 0x7FFFFFFFu) : p.pk_cross) > 200000000u);  // a packet that never leaves: flag it, drop it
   if (runaway) { *A.err = 13; st = S_EMIT; }
   p.st = st;
@@ -1018,7 +1035,9 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         FlightParam FP;
         unsigned int c_cross_wave = 0u;
         bool any_star = true;
-        if (PARAM) { param_begin(F, FP); any_star = __ballot(st == S_FLIGHT && F.star_key >= 0) != 0ull; }
+        if (PARAM || (!VORO && !L3D)) any_star = __ballot(st == S_FLIGHT && F.star_key >= 0) != 0ull;
+        if (PARAM) param_begin(F, FP);
+        const bool flew = (st == S_FLIGHT);
 #pragma unroll 1
         for (int it = 0; it < fly_iters; ++it) {
           // back to the rings as soon as enough lanes have nothing to fly (or after fly_iters crossings)
@@ -1035,14 +1054,16 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
             else finished += fly_step_3d<DARK, LDSE, BIN, VAR, true, MRW>(T, M, A, E_lds, F, c_cross, c_kill, c_dark, dep_ic, dep_v);
             if (BIN) bin_deposit(BS, A.bin, A.E_abs, lane, BP, dep_ic >= 0, dep_ic, dep_v);
           } else {
-            finished += fly_step_2d<DARK, LDSE, MRW, false, VAR>(T, M, A, E_lds, F, c_cross, c_kill, c_dark);
+            finished += fly_step_2d<DARK, LDSE, MRW, false, VAR, true>(T, M, A, E_lds, F, c_cross_wave, c_kill, c_dark, nullptr, nullptr, any_star);
           }
         }
         if (BIN) bin_settle(BS, A.bin, A.E_abs, lane, BP);
-        if (PARAM) {
-          param_end(F, FP);
+        if (PARAM) param_end(F, FP);
+        if (PARAM || (!VORO && !L3D)) {
           if (lane == 0) c_cross += c_cross_wave;
-          if (F.pk_cross > 200000000u && F.st == S_FLIGHT) { *A.err = 13; F.st = S_EMIT; finished += 1; }  // a packet that never leaves: flag it, drop it
+          if (!PARAM && flew && F.st == S_EMIT) { c_kill++; finished += 1; }  // killed at the star's cell (fly_step_2d WAVE)
+          // a packet that never leaves: flag it, drop it (once per visit; MRW: bit 31 is the walk's, see fly_step_2d)
+          if ((MRW && !PARAM ? (F.pk_cross & 0x7FFFFFFFu) : F.pk_cross) > 200000000u && F.st == S_FLIGHT) { *A.err = 13; F.st = S_EMIT; finished += 1; }
         }
         st = F.st;
       }
