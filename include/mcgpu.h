@@ -221,6 +221,8 @@ int mcgpu_set_midplane_snap(mcgpu_ctx *ctx, int on);
  *                      scout pass (exact; see mcgpu_run_mono), 0 = scout every packet first
  *   "voronoi_cache_log_slots"  6..13 (default 13): log2 of the slots of the Voronoi deposit cache
  *   "voronoi_pool_log_records" 6..12 (default 12): log2 of the packet records per workgroup of schedule 3
+ *   "nlte_stats"       1: a launch with non-LTE grains counts the absorptions its waves serve and the wave visits that serve
+ *                      any (mcgpu_get_info "nlte_events", "nlte_visits"; a diagnostic, off by default)
  *   "radiation_field"  bit 0: keep xN_abs, bit 1: keep xJ_abs in the thermal step (mcgpu_fetch_radiation_field);
  *                      cylindrical grids then run the single-role kernel
  * Results do not depend on any of them (same packets, same random numbers) -- except "crossing" = 1, which changes
@@ -434,7 +436,9 @@ int mcgpu_set_I_spec(mcgpu_ctx *ctx, const double *I_spec, const double *I_spec_
  * Out (any may be NULL): frac_E_stars(lambda), frac_E_disk(lambda), E_disk(lambda), prob_E_cell(0:n_cells, lambda).
  * The cumulative distribution also STAYS on the device: a following mcgpu_run_mono of the same wavelength may pass
  * prob_E_cell = NULL.  Fails (MCGPU_ERR_ARG) where the reference stops: no energy at all at this wavelength (:1899).
- * The per-grain branches (lRE_nLTE, lnRE: :1833-1884) are not built -- the engine holds no per-grain temperatures.
+ * After mcgpu_set_Tdust_1grain the lRE_nLTE term (:1832-1850: the emission of the grains out of LTE, from their own
+ * temperatures) is added to the cells' emission; without that call the results are bit for bit what they are with LTE
+ * grains alone.  The lnRE branch (:1852-1884, stochastically heated grains) is not built.
  */
 int mcgpu_repartition_energie(mcgpu_ctx *ctx, int lambda, double wl_um, double E_star, double E_ISM,
                               const float *Tdust, const float *weight_proba_emission,
@@ -675,7 +679,8 @@ int mcgpu_set_variable_dust_s11(mcgpu_ctx *ctx, const float *tab_s11_pos);
  * cells, mem.f90:213-244).  tab_lambda / tab_delta_lambda [n_lambda] in micron (module wavelengths).  Outputs, either
  * may be NULL: the tables in the reference's layouts (of the classes when variable dust is set, else of the single
  * class).  lextra_heating / dudt (the Phantom coupling's non-radiative heating term, :486-494): mcgpu_init_reemission_ex
- * below.  Not built: the per-grain tables of the non-LTE / non-equilibrium grains (:517-532, 552-619).
+ * below.  The per-grain tables of the grains out of LTE (:552-582): mcgpu_init_reemission_nlte.  Not built: those of the
+ * LTE grains in low-memory mode and of the non-equilibrium grains (:517-532, 584-619).
  */
 int mcgpu_init_reemission(mcgpu_ctx *ctx, const double *tab_lambda, const double *tab_delta_lambda,
                           double *log_Qcool, double *kdB_dT_CDF);
@@ -704,8 +709,9 @@ int mcgpu_init_reemission_ex(mcgpu_ctx *ctx, const double *tab_lambda, const dou
  *                             bin 1, normalised (:1141-1154); S1x / S11; s11 dtheta / (2 pi k_sca) for the ray tracer (:1172);
  *                             aniso_method 2: the Henyey-Greenstein phase function (:1190-1194)
  * in the reference's types: default-real tables are rounded after every term.  aniso_method, lsepar_pola, nang,
- * p_lambda_fixed are the context's (mcgpu_set_scattering).  Not built: scattering_method 1 (ksca_CDF), the non-LTE /
- * non-equilibrium grain tables, lphase_function_file, loverwrite_s12, lno_scattering, lqsca_equal_qabs.
+ * p_lambda_fixed are the context's (mcgpu_set_scattering).  Not built: scattering_method 1 (ksca_CDF), the tables of the
+ * non-LTE grains (kabs_nLTE_CDF, Proba_abs_RE_LTE: the host's, mcgpu_set_nlte takes them) and of the non-equilibrium
+ * grains, lphase_function_file, loverwrite_s12, lno_scattering, lqsca_equal_qabs.
  * The grains' tables, all default real, in the reference's layouts (grains.f90:38-54, mem.f90:71-84):
  */
 typedef struct mcgpu_grain_tables {
@@ -762,12 +768,68 @@ int mcgpu_build_ksca_CDF(mcgpu_ctx *ctx, int build, double *ksca_CDF_out);
  *                               returns, mcfost2phantom.f90:361), summed over "threads"
  *   xJ_abs[n_cells * n_lambda]  sum of l * Stokes(1) per cell and wavelength (lxJ_abs_step1), column-major (icell, lambda)
  * Switched on before a thermal launch with mcgpu_set_option(ctx, "radiation_field", bits) -- bit 0: xN_abs, bit 1:
- * xJ_abs; zeroed by a launch unless accumulate is set.  Either pointer may be NULL.
+ * xJ_abs; zeroed by a launch unless accumulate is set.  Either pointer may be NULL.  A launch with non-LTE grains
+ * (mcgpu_set_nlte) keeps xJ_abs by itself, with a cell's wavelengths contiguous on the device; what is returned here is
+ * (icell, lambda) column-major whatever the device layout.
  * xN_abs is counted in 32-bit words on the device: a cell crossed more than 2^32 times between two resets wraps
  * (the reference's default-real counter stops growing at 2^24 instead); with `accumulate` over many 1e8-packet
  * launches fetch and reset it in between.
  */
 int mcgpu_fetch_radiation_field(mcgpu_ctx *ctx, double *xN_abs, double *xJ_abs);
+
+/*
+ * Grains in radiative equilibrium but out of LTE (lRE_nLTE, methode_chauffage = 2, read_param.f90:322-324): one
+ * temperature per grain size and cell.  In the temperature step an absorption by such a grain runs im_reemission_NLTE
+ * (thermal_emission.f90:775-866) instead of im_reemission_LTE, and the step ends in Temp_finale_nLTE (:932-1014).
+ * Scope: the grains grain_RE_nLTE_start..end (numbered 1 .. n_grains_nlte here), alone (lonly_nLTE) or next to LTE grains,
+ * cylindrical grids (2D and 3D), ONE dust class, live and frozen launches, with or without a dark zone.  Refused with
+ * MCGPU_ERR_UNSUPPORTED and a message that says which: stochastically heated grains (n_grains_nRE > 0: lnRE, Temp_nRE,
+ * im_reemission_qRE), variable dust, spherical and Voronoi grids, the modified random walk, scattering method 1 and
+ * mcgpu_multi_run_thermal.  Never called (or n_grains_nlte = 0): every launch is what it is without this section.
+ *
+ * The module arrays in the reference's layouts and types (Fortran order), restricted to the non-LTE grains:
+ *   C_abs_norm(k, lambda)               default real (dust_prop.f90:636)
+ *   kabs_nLTE_CDF(0:n, lambda)          of the single class (dust_prop.f90:931-943)
+ *   Proba_abs_RE_LTE(n_cells, lambda)   or NULL: lonly_nLTE (dust_prop.f90:916-921).  With it a launch draws one more number
+ *                                       per absorption -- who re-emits, dust_transfer.f90:1377-1386 -- and the LTE branch
+ *                                       is the context's own: kappa_abs_LTE of mcgpu_set_opacity is then that of the LTE
+ *                                       grains only, like log_Qcool / kdB_dT_CDF
+ *   grain_density(k, n_cells)           dust_density_o_n_grains(k, icell) * n_grains(k), or NULL (every grain in every cell):
+ *                                       Temp_finale_nLTE gives 0 where a grain has no density (:961)
+ *   log_E_em_1grain(k, T), kdB_dT_1grain_nLTE_CDF(lambda, k, T)   (thermal_emission.f90:552-582) or both NULL: built on the
+ *                                       device by mcgpu_init_reemission_nlte, which must then be called before a launch
+ * Needs the grid, mcgpu_set_opacity and mcgpu_set_thermal (n_cells, n_lambda, n_T, tab_Temp, L_packet_th).
+ * log_E_em_1grain(k, :) must not decrease with T where it is above -1000 (MCGPU_ERR_UNSUPPORTED otherwise): the launch
+ * replaces the reference's ratchet xT_ech_1grain by a search of that row, which is the ratchet's answer exactly when the
+ * row is monotone (the J_abs of a cell only grows during a step).
+ * A launch with non-LTE grains runs the single-role kernel, draws two Philox blocks per interaction (one has no draw to
+ * spare for the choice between LTE and non-LTE grains), and keeps xJ_abs by itself.
+ */
+int mcgpu_set_nlte(mcgpu_ctx *ctx, int n_grains_nlte, int n_grains_nRE, const float *C_abs_norm,
+                   const double *kabs_nLTE_CDF, const double *Proba_abs_RE_LTE, const double *grain_density,
+                   const double *log_E_em_1grain, const double *kdB_dT_1grain_nLTE_CDF);
+/* The per-grain re-emission tables built on the device from C_abs_norm (thermal_emission.f90:552-582; unlike the LTE
+ * table: no subtraction of the tab_Temp(1) term, no density, and the CDF's sum starts at the second wavelength).  Outputs
+ * (either may be NULL) in the reference's layouts.  MCGPU_ERR_UNSUPPORTED when a row of log_E_em_1grain decreases. */
+int mcgpu_init_reemission_nlte(mcgpu_ctx *ctx, const double *tab_lambda, const double *tab_delta_lambda,
+                               double *log_E_em_1grain, double *kdB_dT_1grain_nLTE_CDF);
+/* J0(n_cells, n_lambda) (radiation_field.f90:27; init_reemission sets volume * B(lambda, T_min) * cst_E); NULL: zeros.
+ * A frozen launch (mcgpu_run_opts.frozen = 1) evaluates J_abs on J0 alone -- the analogue of mcgpu_set_E_prior:
+ * reproducible --, a live one on xJ_abs * n_replicas + J0, the way the LTE branch scales the live E_abs.  A frozen launch
+ * needs mcgpu_set_E_prior only when LTE grains are there too (Proba_abs_RE_LTE given). */
+int mcgpu_set_J0(mcgpu_ctx *ctx, const double *J0);
+/* Temp_finale_nLTE (:932-1014): Tdust_1grain(k, n_cells), default real, from the host's xJ_abs(n_cells, n_lambda) or
+ * (NULL) from the device's of the last non-LTE launch(es), plus J0.  T_min (mcgpu_set_thermal's tab_Temp(1) floor) below
+ * the table, 0 where the grain has no density in the cell. */
+int mcgpu_temp_finale_nlte(mcgpu_ctx *ctx, const double *xJ_abs, float *Tdust_1grain);
+/* Tdust_1grain(k, n_cells) and grain_density(k, n_cells) for the lRE_nLTE term of mcgpu_repartition_energie
+ * (thermal_emission.f90:1832-1850); Tdust_1grain = NULL: off again.  Needs mcgpu_set_nlte (C_abs_norm) and belongs to those
+ * tables: a later mcgpu_set_nlte (also with n_grains_nlte = 0) or a new grid drops it. */
+int mcgpu_set_Tdust_1grain(mcgpu_ctx *ctx, const float *Tdust_1grain, const double *grain_density);
+/* Probe: n re-emission events evaluated on J0 (as a frozen launch does), one per wave, by the device function the launch
+ * runs.  icell, lambda0 1-based; out: the grain (1-based), T_int, Temp and the new wavelength (1-based). */
+int mcgpu_probe_reemission_nlte(mcgpu_ctx *ctx, int n, const int *icell, const int *lambda0, const float *rand1,
+                                const float *rand2, int *k_out, int *T_int_out, double *Temp_out, int *lambda_out);
 
 /*
  * Modified random walk (module MRW, MRW.f90; the call site dust_transfer.f90:1222-1239 is commented out in the

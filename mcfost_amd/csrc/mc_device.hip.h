@@ -23,6 +23,8 @@
 #endif
 #include <stdint.h>
 
+#include "mc_nlte.hip.h"  // the grains out of LTE (thermal_body<..., NLTE = true>)
+
 #ifndef MCGPU_CROSS
 #define MCGPU_CROSS cross_cell_lean  // (tests/emu can substitute the branch-for-branch form of tests/emu/cross_cell_literal.h)
 #endif
@@ -1307,6 +1309,12 @@ __device__ inline void radiation_field_extras(const DevModel& M, const RunArgs& 
   if (A.xJ_abs) atomic_add_f64(&A.xJ_abs[(size_t)ic + (size_t)M.n_cells * (size_t)(lambda - 1)], l_S0);
 }
 
+// ... of a non-LTE launch: xJ_abs with a cell's wavelengths contiguous (mc_nlte.hip.h), still one FP64 atomic per crossing
+__device__ inline void nlte_field(const RunArgs& A, const NlteArgs& N, int ic, int lambda, double l_S0) {
+  if (A.xN_abs) atomicAdd(&A.xN_abs[ic], 1ull);
+  atomic_add_f64(&N.xJ[(size_t)ic * (size_t)N.ldJ + (size_t)(lambda - 1)], l_S0);
+}
+
 // ---------------------------------------------------------------------------
 // Deposit cache: 2^log_ns slots of (cell id, partial sum) in LDS, for grids whose absorbed-energy array does not
 // fit in LDS (3D cylindrical: 5.76 MB; Voronoi).  The deposits are extremely concentrated (every packet starts in
@@ -1917,8 +1925,11 @@ struct SphEmitOps {
 // (global_atomic_add_f64), the only option for 3D grids (5.76 MB at 720 000
 // cells).
 // SPH: the grid operators of spherical_grid.f90 instead of cylindrical_grid.f90 (same cell identity and mapping).
-template <bool L3D, bool POLA, bool DARK, bool LDSE, bool SPH = false, bool MRW = false, bool VAR = false>
-__device__ __forceinline__ void thermal_body(const DevModel& M, const RunArgs& A, double* lds_base) {
+// NLTE (k_thermal_nlte, kern_nlte.hip): grains in radiative equilibrium out of LTE (mc_nlte.hip.h) -- the absorptions they
+// take are served by the whole wave, one after the other, and the launch keeps xJ_abs with a cell's wavelengths contiguous
+// (N->xJ) instead of A.xJ_abs.  Every NLTE block below is compiled out of the other instantiations.
+template <bool L3D, bool POLA, bool DARK, bool LDSE, bool SPH = false, bool MRW = false, bool VAR = false, bool NLTE = false>
+__device__ __forceinline__ void thermal_body(const DevModel& M, const RunArgs& A, double* lds_base, const NlteArgs* N = nullptr) {
   double* const E_lds = lds_base;  // [n_cells] when LDSE
   const Lds T = lds_carve(lds_base + (LDSE ? M.n_cells : 0), M);
   lds_stage(T, M);
@@ -2033,6 +2044,64 @@ __device__ __forceinline__ void thermal_body(const DevModel& M, const RunArgs& A
 
     TP_ADD(tp_emit);
     // ---- INTERACT: scatter or absorb + re-emit (dust_transfer.f90:1260-1402)
+    if constexpr (NLTE) {
+      // (the wave is converged here.)  Two Philox blocks per event: with LTE grains next to the non-LTE ones the reference
+      // draws one more number per absorption -- who re-emits (dust_transfer.f90:1377-1386) -- and one block has none to spare
+      float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      const bool inter = st == S_INTERACT;
+      int ic = 0;
+      bool nl = false;
+      if (inter) {
+        rng.interaction_event(g, true);
+        tau_rand = g[5];
+        ic = cell_index<L3D>(n_rad, nz, ri, zj, k);
+        const bool scat = g[0] < T.albedo[lambda - 1];
+        nl = !scat && !(N->proba && (double)g[6] <= N->proba[(size_t)ic + (size_t)M.n_cells * (size_t)(lambda - 1)]);
+      }
+      // the absorptions by non-LTE grains, one after the other, each by the whole wave (mc_nlte.hip.h)
+      int lambda_new = lambda;
+      unsigned long long todo = __ballot(nl);
+      if (N->stats && todo && lane == 0) { atomicAdd(&N->stats[0], (unsigned long long)__popcll(todo)); atomicAdd(&N->stats[1], 1ull); }
+#ifdef MCGPU_NLTE_ONE_LANE   // tuning build: every lane runs its own event (the form the wave-served one is measured against)
+      todo = 0ull;
+      if (nl) lambda_new = nlte_event<false>(*N, M.volume[ic], ic, lambda, g[1], g[2], !A.frozen, A.qscale, lane).lambda;
+#endif
+      while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1ull;
+        const int ic_s = nlte_readlane(ic, src), lambda_s = nlte_readlane(lambda, src);
+        const float r1 = nlte_readlane_f(g[1], src), r2 = nlte_readlane_f(g[2], src);
+        const NlteEvent ev = nlte_event(*N, M.volume[ic_s], ic_s, lambda_s, r1, r2, !A.frozen, A.qscale, lane);
+        if (lane == src) lambda_new = ev.lambda;
+      }
+      if (inter) {
+        double u1, v1, w1;
+        if (nl) {
+          // the rest of the absorb branch (interact_direction / interact_stokes): isotropic direction, unpolarised
+          c_abs++;
+          flag_star = false;
+          flag_scatt = false;
+          lambda = lambda_new;
+          cdapres_pi(2.0 * (double)g[3] - 1.0, 2.0 * (double)g[4] - 1.0, 0.0, 0.0, 1.0, u1, v1, w1);
+          S[1] = 0.0; S[2] = 0.0; S[3] = 0.0;
+        } else {
+          // a scattering, or an absorption by the LTE grains: the context's own branch (kappa_abs_LTE = the LTE grains')
+          interact<POLA>(T, M, g, lambda, u, v, w, u1, v1, w1, S, flag_star, flag_scatt, c_scatt, c_abs, [&]() {
+            double E;
+            if (A.frozen) E = A.E_prior[ic];
+            else {
+              E = __hip_atomic_load(&A.E_abs[ic], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              if (LDSE) E += E_lds[ic] * (double)gridDim.x;
+              E *= A.qscale;
+            }
+            return E;
+          }, M.volume + ic);
+        }
+        if (!flag_scatt) flag_ism = false;
+        u = u1; v = v1; w = w1;
+        st = S_NEWFLIGHT;
+      }
+    } else
     if (st == S_INTERACT) {
       float g[8];
       rng.interaction_event(g, M.m1 != 0);
@@ -2160,6 +2229,7 @@ __device__ __forceinline__ void thermal_body(const DevModel& M, const RunArgs& A
             if (tau > extr) {
               const double lc = l * (extr / tau);
               if (real_cell && !MCGPU_DIAG(A.flags, 1)) deposit<LDSE>(A.E_abs, E_lds, ic, kabs_c * lc * S[0]);
+              if constexpr (NLTE) { if (real_cell) nlte_field(A, *N, ic, lambda, lc * S[0]); } else
               if (real_cell) radiation_field_extras(M, A, ic, lambda, lc * S[0]);
               x = x + lc * u;
               y = y + lc * v;
@@ -2171,6 +2241,7 @@ __device__ __forceinline__ void thermal_body(const DevModel& M, const RunArgs& A
               first_cross = false;
               extr = extr - tau;
               if (real_cell && !MCGPU_DIAG(A.flags, 1)) deposit<LDSE>(A.E_abs, E_lds, ic, kabs_c * l * S[0]);
+              if constexpr (NLTE) { if (real_cell) nlte_field(A, *N, ic, lambda, l * S[0]); } else
               if (real_cell) radiation_field_extras(M, A, ic, lambda, l * S[0]);
               if (DARK) { xo = x; yo = y; zo = z; ri_o = ri; zj_o = zj; k_o = k; }
               x = x1; y = y1; z = z1;

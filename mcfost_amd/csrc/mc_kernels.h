@@ -40,6 +40,14 @@ const void* kpick_mono(bool l3d, bool pola, bool dark, bool scout, bool f32, boo
 const void* kpick_mono_sph(bool l3d, bool pola, bool scout, bool f32);
 const void* kpick_mono_voro(bool pola, bool scout, bool f32);
 
+// kern_nlte.hip: the grains out of LTE (mc_nlte.hip.h) -- k_thermal_nlte (cylindrical grids, one dust class, no random
+// walk), k_probe_reemission_nlte, k_temp_finale_nlte, k_init_reemission_nlte, k_repart_nlte
+const void* kpick_thermal_nlte(bool lds, bool l3d, bool pola, bool dark);
+const void* kpick_probe_reemission_nlte();
+const void* kpick_temp_finale_nlte();
+const void* kpick_init_reemission_nlte();
+const void* kpick_repart_nlte();
+
 // a run-time bool as a compile-time one: bsel(b, [&](auto B) { ... MCGPU_BV(B) ... })
 template <class F>
 inline const void* bsel(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }

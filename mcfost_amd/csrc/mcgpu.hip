@@ -139,6 +139,7 @@ struct mcgpu_ctx {
   int opt_cache_log_slots = 13;  // Voronoi deposit cache: 2^13 slots = 96 KB of LDS
   int opt_crossing = 0;          // 1: the flight-parametric 2D crossing in the role kernel's flying waves (statistical parity only)
   int opt_pool_log_rec = 12;     // Voronoi pool schedule: 2^12 packet records per workgroup (mc_voronoi_pool.hip.h)
+  int opt_nlte_stats = 0;        // 1: a non-LTE launch counts the events its waves serve (mcgpu_get_info "nlte_events" / "nlte_visits")
   int opt_radiation_field = 0;   // bit 0: xN_abs, bit 1: xJ_abs (thermal step; radiation_field.f90:54-55)
   unsigned long long* d_xN = nullptr;  // [n_cells] (64-bit: a hot cell passes 2^32 segments within one 1e9-packet run)
   double* d_xJ = nullptr;        // (n_cells, n_lambda)
@@ -197,9 +198,27 @@ struct mcgpu_ctx {
   size_t pool_bytes = 0;
   VpBlob* d_pool_blob = nullptr;   // ... and the copy of a launch's arguments its emission phase reads
   VpBlob h_pool_blob;
+  // grains out of LTE (mc_nlte.hip.h; mcgpu_set_nlte): n_grains = 0: off
+  struct {
+    int n_grains = 0;
+    bool mixed = false;            // Proba_abs_RE_LTE was given (LTE grains next to the non-LTE ones)
+    bool tables_pending = false;   // log_E_em_1grain / the CDF were left to mcgpu_init_reemission_nlte
+    float* d_Cabs = nullptr;
+    double *d_kcdf = nullptr, *d_proba = nullptr, *d_dens = nullptr, *d_lE = nullptr, *d_cdf = nullptr;
+    double *d_J0 = nullptr, *d_xJ = nullptr;   // [n_cells][ldJ]
+    unsigned long long* d_stats = nullptr;     // [2] events served / wave visits of the last launch
+    bool xJ_last = false;          // the last thermal launch kept xJ_abs in d_xJ (mcgpu_fetch_radiation_field)
+    // mcgpu_set_Tdust_1grain: the lRE_nLTE term of mcgpu_repartition_energie
+    float* d_T1 = nullptr;         // [n_cells][n_grains]
+    double* d_T1_dens = nullptr;   // [n_cells][n_grains]
+    int T1_grains = 0;
+    int dim_lambda = 0, dim_T = 0, dim_cells = 0;   // the model's sizes when the tables were set
+    size_t J0_n = 0, xJ_n = 0;                      // doubles of d_J0 / d_xJ
+  } nl;
 };
 
 static void bin_release(mcgpu_ctx* ctx);
+static void nlte_release(mcgpu_ctx* ctx, bool all);
 static void grid_release(mcgpu_ctx* ctx);
 static int tail_threshold(const mcgpu_ctx* ctx);
 
@@ -287,6 +306,7 @@ extern "C" int mcgpu_destroy(mcgpu_ctx* ctx) {
   if (ctx->d_counters) hipFree(ctx->d_counters);
   if (ctx->d_xN) hipFree(ctx->d_xN);
   if (ctx->d_xJ) hipFree(ctx->d_xJ);
+  nlte_release(ctx, true);
   if (ctx->d_err) hipFree(ctx->d_err);
   if (ctx->d_E_prior) hipFree(ctx->d_E_prior);
   if (ctx->d_xI) hipFree(ctx->d_xI);
@@ -545,6 +565,7 @@ static void grid_release(mcgpu_ctx* ctx) {
   ctx->d_xN = nullptr;
   if (ctx->d_xJ) hipFree(ctx->d_xJ);
   ctx->d_xJ = nullptr;
+  nlte_release(ctx, true);   // (the non-LTE tables, J0 and xJ_abs are per cell)
 }
 
 static void bin_release(mcgpu_ctx* ctx) {
@@ -586,6 +607,7 @@ extern "C" int mcgpu_set_option(mcgpu_ctx* ctx, const char* name, int value) {
   else if (!strcmp(name, "crossing")) { if (value < 0 || value > 1) return fail(ctx, MCGPU_ERR_ARG, "crossing: 0 or 1"); ctx->opt_crossing = value; }
   else if (!strcmp(name, "voronoi_pool_log_records")) { if (value < 6 || value > VP_MAX_LOG_REC) return fail(ctx, MCGPU_ERR_ARG, "voronoi_pool_log_records: 6..12"); ctx->opt_pool_log_rec = value; }
   else if (!strcmp(name, "voronoi_cache_log_slots")) { if (value < 6 || value > 13) return fail(ctx, MCGPU_ERR_ARG, "voronoi_cache_log_slots: 6..13"); ctx->opt_cache_log_slots = value; }
+  else if (!strcmp(name, "nlte_stats")) ctx->opt_nlte_stats = value ? 1 : 0;
   else if (!strcmp(name, "radiation_field")) { if (value < 0 || value > 3) return fail(ctx, MCGPU_ERR_ARG, "radiation_field: bit 0 xN_abs, bit 1 xJ_abs"); ctx->opt_radiation_field = value; }
   else return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_option: unknown option");
   return MCGPU_OK;
@@ -600,6 +622,14 @@ extern "C" int mcgpu_get_info(mcgpu_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "bin_chunks")) *value = ctx->bin_chunks;
   else if (!strcmp(name, "bin_deposits_per_packet")) *value = ctx->bin_dep_per_packet;
   else if (!strcmp(name, "tail_threshold")) *value = tail_threshold(ctx);
+  else if (!strcmp(name, "nlte_events") || !strcmp(name, "nlte_visits")) {   // the last non-LTE launch: absorptions served by
+    unsigned long long v[2] = {0ull, 0ull};                                  // whole waves, and wave visits that served any
+    if (ctx->nl.d_stats) {
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      HIPCHK(hipMemcpy(v, ctx->nl.d_stats, sizeof(v), hipMemcpyDeviceToHost));
+    }
+    *value = (double)v[name[5] == 'e' ? 0 : 1];
+  }
   else if (!strcmp(name, "tail_ms")) {   // k_tail's share of the last thermal launch (0: that launch had no tail kernel)
     *value = 0.0;
     if (ctx->launched && ctx->tail_launched) {
@@ -1529,6 +1559,19 @@ static int launch_tail(mcgpu_ctx* ctx, const RunArgs& A_in, const void* carry, c
 }
 
 // the persistent packet kernel of the cylindrical grids (mc_roles.hip.h, mc_device.hip.h)
+// the single-role kernels' persistent grid: as many workgroups as the LDS footprint lets reside, no more than the packets need
+static int persistent_blocks(const mcgpu_ctx* ctx, size_t lds_k, int threads, unsigned long long n_packets) {
+  const size_t lds_cap = 160 * 1024;
+  int per_cu = (int)(lds_cap / (lds_k > 0 ? lds_k : 1));
+  const int cap = 2048 / threads;  // waves
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu > cap) per_cu = cap;
+  int blocks = ctx->prop.multiProcessorCount * per_cu;
+  const unsigned long long need = (n_packets + threads - 1) / threads;
+  if ((unsigned long long)blocks > need) blocks = (int)(need ? need : 1);
+  return blocks;
+}
+
 static int launch_mega(mcgpu_ctx* ctx, const RunArgs& A, bool use_lds, int grid_blocks, int block_threads) {
   const DevModel& M = ctx->M;
   const size_t lds = lds_bytes(M);
@@ -1537,17 +1580,7 @@ static int launch_mega(mcgpu_ctx* ctx, const RunArgs& A, bool use_lds, int grid_
   const int max_threads = use_lds ? MCGPU_LDS_BLOCK : 256;
   const int threads = (block_threads > 0 && block_threads <= max_threads) ? block_threads : max_threads;
   if (threads % 64) return fail(ctx, MCGPU_ERR_ARG, "block_threads must be a multiple of 64");
-  int blocks = grid_blocks;
-  if (blocks <= 0) {
-    // persistent grid: as many workgroups as the LDS footprint lets reside
-    int per_cu = (int)(lds_cap / (lds_k > 0 ? lds_k : 1));
-    const int cap = 2048 / threads;  // waves
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu > cap) per_cu = cap;
-    blocks = ctx->prop.multiProcessorCount * per_cu;
-    const unsigned long long need = (A.n_packets + threads - 1) / threads;
-    if ((unsigned long long)blocks > need) blocks = (int)(need ? need : 1);
-  }
+  const int blocks = grid_blocks > 0 ? grid_blocks : persistent_blocks(ctx, lds_k, threads, A.n_packets);
   const bool pola = ctx->lsepar_pola != 0, dark = M.dark != nullptr, l3d = M.l3D != 0;
   hipError_t e;
   // Waves with roles and LDS packet queues (mc_roles.hip.h): the default wherever the queues fit next to the
@@ -2020,11 +2053,14 @@ static int launch_binned(mcgpu_ctx* ctx, RunArgs A, const mcgpu_run_opts* o) {
   return MCGPU_OK;
 }
 
+static int launch_nlte(mcgpu_ctx* ctx, RunArgs A, const mcgpu_run_opts* o);
+
 extern "C" int mcgpu_launch_thermal(mcgpu_ctx* ctx, const mcgpu_run_opts* o) {
   int rc = ready(ctx);
   if (rc) return rc;
   if (!o) return fail(ctx, MCGPU_ERR_ARG, "null options");
-  if (o->frozen && !ctx->d_E_prior) return fail(ctx, MCGPU_ERR_STATE, "frozen mode needs mcgpu_set_E_prior");
+  // (non-LTE grains alone: a frozen launch reads J0 and never E_prior)
+  if (o->frozen && !ctx->d_E_prior && !(ctx->nl.n_grains && !ctx->nl.mixed)) return fail(ctx, MCGPU_ERR_STATE, "frozen mode needs mcgpu_set_E_prior");
   HIPCHK(hipSetDevice(ctx->device));
   if ((rc = ensure_accum(ctx))) return rc;
   const DevModel& M = ctx->M;
@@ -2068,6 +2104,14 @@ extern "C" int mcgpu_launch_thermal(mcgpu_ctx* ctx, const mcgpu_run_opts* o) {
     if (!ctx->d_xJ) { HIPCHK(hipMalloc((void**)&ctx->d_xJ, nj * sizeof(double))); HIPCHK(hipMemset(ctx->d_xJ, 0, nj * sizeof(double))); }
     if (!o->accumulate) HIPCHK(hipMemsetAsync(ctx->d_xJ, 0, nj * sizeof(double), ctx->stream));
     A.xJ_abs = ctx->d_xJ;
+  }
+  ctx->nl.xJ_last = false;
+  if (ctx->nl.n_grains) {   // grains out of LTE: the non-LTE instantiation of the single-role kernel (kern_nlte.hip)
+    int rcn = launch_nlte(ctx, A, o);
+    if (rcn) return rcn;
+    ctx->launched = true;
+    ctx->accum_packets = (o->accumulate ? ctx->accum_packets : 0.0) + (double)o->n_packets;
+    return MCGPU_OK;
   }
   if (ctx->voro) {
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
@@ -2191,7 +2235,13 @@ extern "C" int mcgpu_fetch_radiation_field(mcgpu_ctx* ctx, double* xN_abs, doubl
     HIPCHK(hipMemcpy(h.data(), ctx->d_xN, (size_t)M.n_cells * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (int i = 0; i < M.n_cells; ++i) xN_abs[i] = (double)h[i];
   }
-  if (xJ_abs) {
+  if (xJ_abs && ctx->nl.xJ_last) {   // a non-LTE launch keeps a cell's wavelengths contiguous: back to (icell, lambda)
+    const int ld = nlte_ldJ(M.n_lambda);
+    std::vector<double> h((size_t)M.n_cells * ld);
+    HIPCHK(hipMemcpy(h.data(), ctx->nl.d_xJ, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int l = 0; l < M.n_lambda; ++l)
+      for (int i = 0; i < M.n_cells; ++i) xJ_abs[(size_t)i + (size_t)M.n_cells * l] = h[(size_t)i * ld + l];
+  } else if (xJ_abs) {
     if (!ctx->d_xJ) return fail(ctx, MCGPU_ERR_STATE, "xJ_abs was not accumulated (option radiation_field bit 1)");
     HIPCHK(hipMemcpy(xJ_abs, ctx->d_xJ, (size_t)M.n_cells * M.n_lambda * sizeof(double), hipMemcpyDeviceToHost));
   }
@@ -2264,6 +2314,20 @@ extern "C" int mcgpu_repartition_energie(mcgpu_ctx* ctx, int lambda, double wl_u
   if (!ctx->d_prob_E) HIPCHK(hipMalloc((void**)&ctx->d_prob_E, ((size_t)n + 1) * sizeof(double)));
   const double wl = wl_um * (double)1.e-6f;  // (:1804: the default-real literal 1.e-6)
   hipLaunchKernelGGL(k_repart_E_cell, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, M, lambda, wl, d_T.p, d_w.p, d_E.p, d_Ec.p);
+  if (ctx->nl.d_T1 && (!ctx->nl.d_Cabs || ctx->nl.T1_grains != ctx->nl.n_grains || ctx->nl.dim_lambda != M.n_lambda || ctx->nl.dim_cells != M.n_cells))
+    return fail(ctx, MCGPU_ERR_STATE, "mcgpu_repartition_energie: the grains' temperatures (mcgpu_set_Tdust_1grain) belong to other non-LTE tables or another grid");
+  if (ctx->nl.d_T1) {   // the lRE_nLTE term (thermal_emission.f90:1832-1850; mcgpu_set_Tdust_1grain)
+    int ng = ctx->nl.T1_grains, ldC = 1, nn = n;
+    const float* Cl = ctx->nl.d_Cabs + (size_t)(lambda - 1);   // [n_grains][n_lambda]: the wavelength's column, stride n_lambda
+    ldC = M.n_lambda;
+    const float* T1 = ctx->nl.d_T1;
+    const double *dn = ctx->nl.d_T1_dens, *vol = M.volume;
+    const unsigned char* dk = M.dark;
+    double *pE = d_E.p, *pEc = d_Ec.p;
+    double wl_ = wl;
+    void* args[] = {&nn, &ng, &Cl, &ldC, &wl_, &T1, &dn, &vol, &dk, &pE, &pEc};
+    HIPCHK(hipLaunchKernel(kpick_repart_nlte(), dim3((n + 255) / 256), dim3(256), args, 0, ctx->stream));
+  }
   hipLaunchKernelGGL(k_cumsum_in_order, dim3(1), dim3(SCAN_TILE), 0, ctx->stream, d_Ec.p, d_E.p, n, ctx->d_prob_E, d_tot.p);
   hipLaunchKernelGGL(k_cumsum_normalise, dim3((n + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_prob_E, d_tot.p, n);
   HIPCHK(hipGetLastError());
@@ -3031,6 +3095,326 @@ extern "C" int mcgpu_temp_finale(mcgpu_ctx* ctx, const double* E_abs, float* Tdu
   HIPCHK(hipStreamSynchronize(ctx->stream));
   hipFree(d_T);
   if (d_E) hipFree(d_E);
+  return MCGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Grains in radiative equilibrium out of LTE (lRE_nLTE; mc_nlte.hip.h, kern_nlte.hip): see include/mcgpu.h
+// ---------------------------------------------------------------------------------------------
+static void nlte_release(mcgpu_ctx* ctx, bool all) {
+  auto& n = ctx->nl;
+  void* p[] = {n.d_Cabs, n.d_kcdf, n.d_proba, n.d_dens, n.d_lE, n.d_cdf};
+  for (void* q : p) if (q) hipFree(q);
+  n.d_Cabs = nullptr; n.d_kcdf = n.d_proba = n.d_dens = n.d_lE = n.d_cdf = nullptr;
+  n.n_grains = 0; n.mixed = false; n.tables_pending = false;
+  // (the grains' temperatures of mcgpu_set_Tdust_1grain belong to these tables: the term of mcgpu_repartition_energie reads
+  // C_abs_norm with them, so it goes when they go)
+  if (n.d_T1) hipFree(n.d_T1);
+  if (n.d_T1_dens) hipFree(n.d_T1_dens);
+  n.d_T1 = nullptr; n.d_T1_dens = nullptr; n.T1_grains = 0;
+  if (all) {
+    void* r[] = {n.d_J0, n.d_xJ, n.d_stats};
+    for (void* q : r) if (q) hipFree(q);
+    n.J0_n = n.xJ_n = 0;
+    n.d_J0 = n.d_xJ = nullptr; n.d_stats = nullptr; n.xJ_last = false;
+  }
+}
+
+// a null context: without a device no context can exist (mcgpu_create fails), and the entry points say so
+static int nlte_no_ctx() {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return MCGPU_ERR_NO_DEVICE;
+  return MCGPU_ERR_ARG;
+}
+
+template <typename Tp>
+static hipError_t nlte_put(Tp** d, const Tp* h, size_t n) {
+  hipError_t e = hipMalloc((void**)d, (n ? n : 1) * sizeof(Tp));
+  if (e == hipSuccess) e = hipMemcpy(*d, h, n * sizeof(Tp), hipMemcpyHostToDevice);
+  return e;
+}
+
+// log_E_em_1grain [n_grains][n_T] must not decrease with T where it is above -1000 (the launch searches it)
+static bool nlte_rows_increase(const std::vector<double>& lE, int ng, int nT) {
+  for (int k = 0; k < ng; ++k)
+    for (int t = 1; t < nT; ++t) {
+      const double a = lE[(size_t)k * nT + t - 1], b = lE[(size_t)k * nT + t];
+      if (!(b >= a) && (a > -1000.0 || b > -1000.0)) return false;
+    }
+  return true;
+}
+
+static NlteArgs nlte_args(const mcgpu_ctx* ctx) {
+  NlteArgs N;
+  std::memset(&N, 0, sizeof(N));
+  const DevModel& M = ctx->M;
+  N.n_grains = ctx->nl.n_grains; N.n_lambda = M.n_lambda; N.n_T = M.n_T; N.n_cells = M.n_cells; N.ldJ = nlte_ldJ(M.n_lambda);
+  N.Cabs = ctx->nl.d_Cabs; N.kcdf = ctx->nl.d_kcdf; N.proba = ctx->nl.d_proba; N.lE = ctx->nl.d_lE; N.cdf = ctx->nl.d_cdf;
+  N.tab_Temp = ctx->d_tab_Temp; N.J0 = ctx->nl.d_J0; N.xJ = ctx->nl.d_xJ; N.dens = ctx->nl.d_dens;
+  N.L_packet_th = M.L_packet_th;
+  return N;
+}
+
+extern "C" int mcgpu_set_nlte(mcgpu_ctx* ctx, int n_grains_nlte, int n_grains_nRE, const float* C_abs_norm, const double* kabs_nLTE_CDF,
+                              const double* Proba_abs_RE_LTE, const double* grain_density, const double* log_E_em_1grain,
+                              const double* kdB_dT_1grain_nLTE_CDF) {
+  if (!ctx) return nlte_no_ctx();
+  if (n_grains_nlte < 0 || n_grains_nRE < 0) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_nlte: negative grain count");
+  if (n_grains_nRE > 0)
+    return fail(ctx, MCGPU_ERR_UNSUPPORTED, "mcgpu_set_nlte: stochastically heated grains (lnRE: Temp_nRE, im_reemission_qRE) are not built");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  nlte_release(ctx, false);
+  if (n_grains_nlte == 0) return MCGPU_OK;
+  if (!C_abs_norm || !kabs_nLTE_CDF || ((log_E_em_1grain == nullptr) != (kdB_dT_1grain_nLTE_CDF == nullptr)))
+    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_nlte: C_abs_norm and kabs_nLTE_CDF are needed; the two re-emission tables come together or not at all");
+  if (!ctx->have_grid || !ctx->have_opacity || !ctx->have_thermal)
+    return fail(ctx, MCGPU_ERR_STATE, "mcgpu_set_nlte: set the grid, the opacities and the thermal tables first");
+  const DevModel& M = ctx->M;
+  const int ng = n_grains_nlte, nl = M.n_lambda, nT = M.n_T, nc = M.n_cells;
+  if (nT < 2) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_nlte: at least two sampled temperatures");
+  auto& n = ctx->nl;
+  std::vector<float> C((size_t)ng * nl);   // (k, lambda) -> [k][lambda]
+  for (int l = 0; l < nl; ++l)
+    for (int k = 0; k < ng; ++k) C[(size_t)k * nl + l] = C_abs_norm[(size_t)k + (size_t)ng * l];
+  hipError_t e = nlte_put(&n.d_Cabs, C.data(), C.size());
+  if (e == hipSuccess) e = nlte_put(&n.d_kcdf, kabs_nLTE_CDF, (size_t)(ng + 1) * nl);
+  if (e == hipSuccess && Proba_abs_RE_LTE) e = nlte_put(&n.d_proba, Proba_abs_RE_LTE, (size_t)nc * nl);
+  if (e == hipSuccess && grain_density) e = nlte_put(&n.d_dens, grain_density, (size_t)nc * ng);
+  if (e == hipSuccess) e = hipMalloc((void**)&n.d_lE, (size_t)ng * nT * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&n.d_cdf, (size_t)ng * nT * nl * sizeof(double));
+  if (e == hipSuccess && log_E_em_1grain) {
+    std::vector<double> lE((size_t)ng * nT), cdf((size_t)ng * nT * nl);   // (k, T) -> [k][T]; (lambda, k, T) -> [k][T][lambda]
+    for (int t = 0; t < nT; ++t)
+      for (int k = 0; k < ng; ++k) {
+        lE[(size_t)k * nT + t] = log_E_em_1grain[(size_t)k + (size_t)ng * t];
+        std::memcpy(&cdf[((size_t)k * nT + t) * nl], &kdB_dT_1grain_nLTE_CDF[((size_t)t * ng + k) * nl], (size_t)nl * sizeof(double));
+      }
+    if (!nlte_rows_increase(lE, ng, nT)) {
+      nlte_release(ctx, false);
+      return fail(ctx, MCGPU_ERR_UNSUPPORTED, "mcgpu_set_nlte: log_E_em_1grain(k, :) must increase with T (the launch searches it)");
+    }
+    e = hipMemcpy(n.d_lE, lE.data(), lE.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(n.d_cdf, cdf.data(), cdf.size() * sizeof(double), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) { nlte_release(ctx, false); return fail(ctx, MCGPU_ERR_HIP, hipGetErrorString(e)); }
+  n.n_grains = ng;
+  n.dim_lambda = nl; n.dim_T = nT; n.dim_cells = nc;
+  n.mixed = Proba_abs_RE_LTE != nullptr;
+  n.tables_pending = log_E_em_1grain == nullptr;
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_init_reemission_nlte(mcgpu_ctx* ctx, const double* tab_lambda, const double* tab_delta_lambda,
+                                          double* log_E_em_1grain, double* kdB_dT_1grain_nLTE_CDF) {
+  if (!ctx) return nlte_no_ctx();
+  if (!tab_lambda || !tab_delta_lambda) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_init_reemission_nlte: bad argument");
+  if (!ctx->nl.n_grains) return fail(ctx, MCGPU_ERR_STATE, "mcgpu_init_reemission_nlte: mcgpu_set_nlte first");
+  HIPCHK(hipSetDevice(ctx->device));
+  const DevModel& M = ctx->M;
+  if (ctx->nl.dim_lambda != M.n_lambda || ctx->nl.dim_T != M.n_T || ctx->nl.dim_cells != M.n_cells || !ctx->d_tab_Temp)
+    return fail(ctx, MCGPU_ERR_STATE, "mcgpu_init_reemission_nlte: the non-LTE tables were set for another grid, wavelength or temperature sampling: mcgpu_set_nlte again");
+  const int ng = ctx->nl.n_grains, nl = M.n_lambda, nT = M.n_T;
+  for (int l = 0; l < nl; ++l)
+    if (!(tab_lambda[l] > 0.0) || !(tab_delta_lambda[l] > 0.0))
+      return fail(ctx, MCGPU_ERR_ARG, "mcgpu_init_reemission_nlte: wavelengths and bin widths must be positive");
+  DevBuf<double> d_lam;
+  HIPCHK(d_lam.alloc(2 * (size_t)nl));
+  HIPCHK(hipMemcpy(d_lam.p, tab_lambda, (size_t)nl * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_lam.p + nl, tab_delta_lambda, (size_t)nl * sizeof(double), hipMemcpyHostToDevice));
+  {
+    int a_ng = ng, a_nT = nT, a_nl = nl;
+    const float *tT = ctx->d_tab_Temp, *C = ctx->nl.d_Cabs;
+    const double *lam = d_lam.p, *dlam = d_lam.p + nl;
+    double *lE = ctx->nl.d_lE, *cdf = ctx->nl.d_cdf;
+    void* args[] = {&a_ng, &a_nT, &a_nl, &tT, &lam, &dlam, &C, &lE, &cdf};
+    const int nthr = ng * nT, threads = 64;
+    HIPCHK(hipLaunchKernel(kpick_init_reemission_nlte(), dim3((nthr + threads - 1) / threads), dim3(threads), args, 0, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  std::vector<double> lE((size_t)ng * nT);
+  HIPCHK(hipMemcpy(lE.data(), ctx->nl.d_lE, lE.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (log_E_em_1grain)
+    for (int t = 0; t < nT; ++t)
+      for (int k = 0; k < ng; ++k) log_E_em_1grain[(size_t)k + (size_t)ng * t] = lE[(size_t)k * nT + t];
+  if (kdB_dT_1grain_nLTE_CDF) {
+    std::vector<double> cdf((size_t)ng * nT * nl);
+    HIPCHK(hipMemcpy(cdf.data(), ctx->nl.d_cdf, cdf.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int t = 0; t < nT; ++t)
+      for (int k = 0; k < ng; ++k)
+        std::memcpy(&kdB_dT_1grain_nLTE_CDF[((size_t)t * ng + k) * nl], &cdf[((size_t)k * nT + t) * nl], (size_t)nl * sizeof(double));
+  }
+  if (!nlte_rows_increase(lE, ng, nT)) {
+    ctx->nl.tables_pending = true;
+    return fail(ctx, MCGPU_ERR_UNSUPPORTED, "log_E_em_1grain(k, :) must increase with T (the tables just built do not: no launch until they are replaced)");
+  }
+  ctx->nl.tables_pending = false;
+  return MCGPU_OK;
+}
+
+// (icell, lambda) column-major on the host -> [n_cells][ldJ] on the device
+static hipError_t nlte_put_field(const mcgpu_ctx* ctx, const double* host, double* dev) {
+  const int nc = ctx->M.n_cells, nl = ctx->M.n_lambda, ld = nlte_ldJ(nl);
+  std::vector<double> h((size_t)nc * ld, 0.0);
+  for (int l = 0; l < nl; ++l)
+    for (int i = 0; i < nc; ++i) h[(size_t)i * ld + l] = host[(size_t)i + (size_t)nc * l];
+  return hipMemcpy(dev, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+}
+
+extern "C" int mcgpu_set_J0(mcgpu_ctx* ctx, const double* J0) {
+  if (!ctx) return nlte_no_ctx();
+  if (!ctx->have_grid || !ctx->have_opacity) return fail(ctx, MCGPU_ERR_STATE, "mcgpu_set_J0: set the grid and the opacities first");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (ctx->nl.d_J0) { hipFree(ctx->nl.d_J0); ctx->nl.d_J0 = nullptr; }
+  ctx->nl.J0_n = 0;
+  if (!J0) return MCGPU_OK;
+  ctx->nl.J0_n = (size_t)ctx->M.n_cells * nlte_ldJ(ctx->M.n_lambda);
+  HIPCHK(hipMalloc((void**)&ctx->nl.d_J0, ctx->nl.J0_n * sizeof(double)));
+  HIPCHK(nlte_put_field(ctx, J0, ctx->nl.d_J0));
+  return MCGPU_OK;
+}
+
+// what a non-LTE call cannot run with: says which
+static int nlte_scope(mcgpu_ctx* ctx) {
+  const DevModel& M = ctx->M;
+  if (ctx->voro) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "non-LTE grains on a Voronoi grid are not built (cylindrical grids only)");
+  if (M.grid_sph) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "non-LTE grains on a spherical grid are not built (cylindrical grids only)");
+  // (scattering method 1 runs on a variable-dust context: it is named first)
+  if (M.m1) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "non-LTE grains with scattering method 1 are not built");
+  if (M.n_classes) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "non-LTE grains with variable dust (lvariable_dust) are not built (one dust class only)");
+  if (M.mrw) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "non-LTE grains with the modified random walk are not built");
+  if (ctx->nl.n_grains && (ctx->nl.dim_lambda != M.n_lambda || ctx->nl.dim_T != M.n_T || ctx->nl.dim_cells != M.n_cells))
+    return fail(ctx, MCGPU_ERR_STATE, "the non-LTE tables were set for another grid, wavelength or temperature sampling: mcgpu_set_nlte again");
+  if (ctx->nl.d_J0 && ctx->nl.J0_n != (size_t)M.n_cells * nlte_ldJ(M.n_lambda))
+    return fail(ctx, MCGPU_ERR_STATE, "J0 was set for another grid or wavelength sampling: mcgpu_set_J0 again");
+  if (ctx->nl.tables_pending)
+    return fail(ctx, MCGPU_ERR_STATE, "the per-grain re-emission tables were left to mcgpu_init_reemission_nlte: call it first");
+  if (ctx->nl.n_grains && (M.n_T < 2 || !ctx->d_tab_Temp)) return fail(ctx, MCGPU_ERR_STATE, "non-LTE grains: thermal tables missing");
+  return MCGPU_OK;
+}
+
+static int launch_nlte(mcgpu_ctx* ctx, RunArgs A, const mcgpu_run_opts* o) {
+  int rc = nlte_scope(ctx);
+  if (rc) return rc;
+  const DevModel& M = ctx->M;
+  const size_t nj = (size_t)M.n_cells * nlte_ldJ(M.n_lambda);
+  if (ctx->nl.d_xJ && ctx->nl.xJ_n != nj) { hipFree(ctx->nl.d_xJ); ctx->nl.d_xJ = nullptr; }
+  if (!ctx->nl.d_xJ) { HIPCHK(hipMalloc((void**)&ctx->nl.d_xJ, nj * sizeof(double))); HIPCHK(hipMemset(ctx->nl.d_xJ, 0, nj * sizeof(double))); ctx->nl.xJ_n = nj; }
+  if (!ctx->nl.d_stats) HIPCHK(hipMalloc((void**)&ctx->nl.d_stats, 2 * sizeof(unsigned long long)));
+  if (!o->accumulate) HIPCHK(hipMemsetAsync(ctx->nl.d_xJ, 0, nj * sizeof(double), ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->nl.d_stats, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  A.xJ_abs = nullptr;   // (the launch keeps xJ_abs itself, a cell's wavelengths contiguous: N.xJ)
+  NlteArgs N = nlte_args(ctx);
+  N.stats = ctx->opt_nlte_stats ? ctx->nl.d_stats : nullptr;   // (diagnostic, off by default: tools/nlte_bench.py)
+  // deposits of E_abs: the workgroup's private grid in LDS where it fits next to the tables, HBM atomics otherwise
+  const size_t lds = lds_bytes(M), lds_cap = 160 * 1024;
+  const size_t lds_e = lds + (size_t)M.n_cells * sizeof(double);
+  bool use_lds = lds_e <= lds_cap;
+  if (ctx->opt_deposit == 1) use_lds = false;
+  else if (ctx->opt_deposit == 2 && !use_lds) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "deposit = lds: the grid does not fit in LDS");
+  else if (ctx->opt_deposit == 3) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "deposit = binned: not with non-LTE grains (the single-role kernel)");
+  const size_t lds_k = use_lds ? lds_e : lds;
+  const int max_threads = use_lds ? MCGPU_LDS_BLOCK : 256;
+  const int threads = (o->block_threads > 0 && o->block_threads <= max_threads) ? o->block_threads : max_threads;
+  if (threads % 64) return fail(ctx, MCGPU_ERR_ARG, "block_threads must be a multiple of 64");
+  const int blocks = o->grid_blocks > 0 ? o->grid_blocks : persistent_blocks(ctx, lds_k, threads, A.n_packets);
+  const void* fn = kpick_thermal_nlte(use_lds, M.l3D != 0, ctx->lsepar_pola != 0, M.dark != nullptr);
+  HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
+  HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k));
+  void* args[] = {(void*)&M, (void*)&A, (void*)&N};
+  HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(threads), args, lds_k, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->nl.xJ_last = true;
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_temp_finale_nlte(mcgpu_ctx* ctx, const double* xJ_abs, float* Tdust_1grain) {
+  if (!ctx) return nlte_no_ctx();
+  if (!Tdust_1grain) return fail(ctx, MCGPU_ERR_ARG, "null Tdust_1grain");
+  if (!ctx->nl.n_grains) return fail(ctx, MCGPU_ERR_STATE, "mcgpu_temp_finale_nlte: mcgpu_set_nlte first");
+  int rc = nlte_scope(ctx);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const DevModel& M = ctx->M;
+  NlteArgs N = nlte_args(ctx);
+  DevBuf<double> d_x;
+  if (xJ_abs) {
+    HIPCHK(d_x.alloc((size_t)M.n_cells * N.ldJ));
+    HIPCHK(nlte_put_field(ctx, xJ_abs, d_x.p));
+    N.xJ = d_x.p;
+  } else if (!ctx->nl.d_xJ || ctx->nl.xJ_n != (size_t)M.n_cells * N.ldJ) {
+    return fail(ctx, MCGPU_ERR_STATE, "no xJ_abs to reduce: no non-LTE launch on this model yet");
+  }
+  const size_t nout = (size_t)M.n_cells * N.n_grains;
+  DevBuf<float> d_T;
+  HIPCHK(d_T.alloc(nout));
+  const double* vol = M.volume;
+  float T_min = ctx->T_min;
+  float* out = d_T.p;
+  void* args[] = {&N, &vol, &T_min, &out};
+  HIPCHK(hipLaunchKernel(kpick_temp_finale_nlte(), dim3((M.n_cells + 3) / 4), dim3(256), args, 0, ctx->stream));
+  HIPCHK(hipMemcpyAsync(Tdust_1grain, d_T.p, nout * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_set_Tdust_1grain(mcgpu_ctx* ctx, const float* Tdust_1grain, const double* grain_density) {
+  if (!ctx) return nlte_no_ctx();
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (ctx->nl.d_T1) { hipFree(ctx->nl.d_T1); ctx->nl.d_T1 = nullptr; }
+  if (ctx->nl.d_T1_dens) { hipFree(ctx->nl.d_T1_dens); ctx->nl.d_T1_dens = nullptr; }
+  ctx->nl.T1_grains = 0;
+  if (!Tdust_1grain) return MCGPU_OK;   // (off again)
+  if (!grain_density) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_Tdust_1grain: the grains' densities are needed");
+  if (!ctx->nl.n_grains) return fail(ctx, MCGPU_ERR_STATE, "mcgpu_set_Tdust_1grain: mcgpu_set_nlte first (C_abs_norm)");
+  if (ctx->nl.dim_lambda != ctx->M.n_lambda || ctx->nl.dim_cells != ctx->M.n_cells)
+    return fail(ctx, MCGPU_ERR_STATE, "mcgpu_set_Tdust_1grain: the non-LTE tables were set for another grid or wavelength sampling");
+  const size_t n = (size_t)ctx->M.n_cells * ctx->nl.n_grains;
+  hipError_t e = nlte_put(&ctx->nl.d_T1, Tdust_1grain, n);
+  if (e == hipSuccess) e = nlte_put(&ctx->nl.d_T1_dens, grain_density, n);
+  if (e != hipSuccess) return fail(ctx, MCGPU_ERR_HIP, hipGetErrorString(e));
+  ctx->nl.T1_grains = ctx->nl.n_grains;
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_probe_reemission_nlte(mcgpu_ctx* ctx, int n, const int* icell, const int* lambda0, const float* rand1,
+                                           const float* rand2, int* k_out, int* T_int_out, double* Temp_out, int* lambda_out) {
+  if (!ctx) return nlte_no_ctx();
+  if (n < 0 || (n && (!icell || !lambda0 || !rand1 || !rand2 || !k_out || !T_int_out || !Temp_out || !lambda_out)))
+    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_reemission_nlte: bad argument");
+  if (!ctx->nl.n_grains) return fail(ctx, MCGPU_ERR_STATE, "mcgpu_probe_reemission_nlte: mcgpu_set_nlte first");
+  int rc = nlte_scope(ctx);
+  if (rc) return rc;
+  const DevModel& M = ctx->M;
+  for (int i = 0; i < n; ++i)
+    if (icell[i] < 1 || icell[i] > M.n_cells || lambda0[i] < 1 || lambda0[i] > M.n_lambda)
+      return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_reemission_nlte: cell or wavelength out of range");
+  if (!n) return MCGPU_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  NlteArgs N = nlte_args(ctx);
+  DevBuf<int> d_i, d_o;
+  DevBuf<float> d_r;
+  DevBuf<double> d_T;
+  HIPCHK(d_i.alloc(2 * (size_t)n)); HIPCHK(d_o.alloc(3 * (size_t)n)); HIPCHK(d_r.alloc(2 * (size_t)n)); HIPCHK(d_T.alloc((size_t)n));
+  HIPCHK(hipMemcpy(d_i.p, icell, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_i.p + n, lambda0, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_r.p, rand1, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_r.p + n, rand2, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  const double* vol = M.volume;
+  const int *pi = d_i.p, *pl = d_i.p + n;
+  const float *p1 = d_r.p, *p2 = d_r.p + n;
+  int *ok = d_o.p, *oT = d_o.p + n, *ol = d_o.p + 2 * (size_t)n;
+  double* oTemp = d_T.p;
+  void* args[] = {&N, &vol, &n, &pi, &pl, &p1, &p2, &ok, &oT, &oTemp, &ol};
+  HIPCHK(hipLaunchKernel(kpick_probe_reemission_nlte(), dim3((n + 3) / 4), dim3(256), args, 0, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(k_out, ok, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(T_int_out, oT, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(lambda_out, ol, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(Temp_out, oTemp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return MCGPU_OK;
 }
 
@@ -3865,6 +4249,11 @@ extern "C" int mcgpu_multi_run_thermal(mcgpu_multi* mm, const mcgpu_run_opts* op
                                        double* n_sent, uint64_t* counters, double* kernel_ms) {
   if (!mm || !opts) return MCGPU_ERR_ARG;
   const int n = mm->n_dev;
+  for (int i = 0; i < n; ++i)
+    if (mm->ctx[i]->nl.n_grains) {
+      mm->err = "mcgpu_multi_run_thermal with non-LTE grains (mcgpu_set_nlte) is not built: xJ_abs is not reduced over the devices";
+      return MCGPU_ERR_UNSUPPORTED;
+    }
   auto failed = [&](int i, int rc) { mm->err = "device " + std::to_string(i) + ": " + mcgpu_last_error(mm->ctx[i]); multi_drain(mm); return rc; };
   int rc;
   if (opts->accumulate) { if ((rc = multi_prepare_accumulate(mm, 0))) { multi_drain(mm); return rc; } }

@@ -37,6 +37,8 @@ ABI_SYMBOLS = (
     "mcgpu_get_xI_precision", "mcgpu_set_option", "mcgpu_get_info", "mcgpu_counters_to_accum", "mcgpu_counters_from_accum",
     "mcgpu_set_grid_sph", "mcgpu_temp_approx_diffusion_vertical", "mcgpu_set_mrw", "mcgpu_fetch_radiation_field", "mcgpu_set_variable_dust", "mcgpu_rt1_stars_map_sed", "mcgpu_define_dark_zone", "mcgpu_init_reemission", "mcgpu_multi_create", "mcgpu_multi_destroy", "mcgpu_multi_size", "mcgpu_multi_ctx", "mcgpu_multi_last_error",
     "mcgpu_repartition_energie", "mcgpu_opacity", "mcgpu_set_variable_dust_s11", "mcgpu_set_scattering_method1", "mcgpu_set_rt2", "mcgpu_fetch_I_spec", "mcgpu_rt1_stars_map_image", "mcgpu_set_I_spec", "mcgpu_rt2_source", "mcgpu_rt2_dust_map", "mcgpu_rt2_image", "mcgpu_shard_packets", "mcgpu_multi_run_thermal", "mcgpu_multi_run_mono", "mcgpu_multi_run_sed", "mcgpu_multi_rccl_ranks", "mcgpu_multi_create_ex", "mcgpu_multi_reductions", "mcgpu_set_mrw_exit_spectrum", "mcgpu_voronoi_tesselation", "mcgpu_build_ksca_CDF", "mcgpu_init_reemission_ex", "mcgpu_tau_maps",
+    "mcgpu_set_nlte", "mcgpu_init_reemission_nlte", "mcgpu_set_J0", "mcgpu_temp_finale_nlte", "mcgpu_set_Tdust_1grain",
+    "mcgpu_probe_reemission_nlte",
 )
 
 
@@ -141,6 +143,7 @@ class Engine:
     def __init__(self, model, n_packets_total, device: int = 0, _borrowed_ctx=None):
         self.lib = load_library()
         self.model = model
+        self.nlte = None   # tables of the grains out of LTE (set_nlte)
         self.ctx = C.c_void_p()
         self._owns_ctx = _borrowed_ctx is None
         if _borrowed_ctx is not None:   # a context of a MultiEngine: it creates and destroys it
@@ -369,6 +372,68 @@ class Engine:
             C.c_double(float(ufac_implicit)),
             _p(lq, C.c_double) if fetch else None, _p(cdf, C.c_double) if fetch else None), "mcgpu_init_reemission")
         return lq, cdf
+
+    def set_nlte(self, nl, build_on_device=False, n_grains_nRE=0):
+        """Grains out of LTE (``mcgpu_set_nlte``): ``nl`` as ``host.model.init_nlte`` builds it (None: off again).
+        ``build_on_device``: leave ``log_E_em_1grain`` and the CDF to ``init_reemission_nlte``."""
+        if nl is None:
+            self._chk(self.lib.mcgpu_set_nlte(self.ctx, 0, 0, None, None, None, None, None, None), "mcgpu_set_nlte")
+            self.nlte = None
+            return
+        d = C.c_double
+        opt = lambda a, dt, ct: None if a is None else _p(_a(a, dt), ct)
+        host_tabs = not build_on_device
+        self._chk(self.lib.mcgpu_set_nlte(
+            self.ctx, C.c_int(int(nl["n_grains"])), C.c_int(int(n_grains_nRE)), _p(_a(nl["C_abs_norm"], np.float32), C.c_float),
+            _p(_a(nl["kabs_nLTE_CDF"], np.float64), d), opt(nl.get("Proba_abs_RE_LTE"), np.float64, d),
+            opt(nl.get("grain_density"), np.float64, d),
+            opt(nl["log_E_em_1grain"], np.float64, d) if host_tabs else None,
+            opt(nl["kdB_dT_1grain_nLTE_CDF"], np.float64, d) if host_tabs else None), "mcgpu_set_nlte")
+        self.nlte = nl
+
+    def init_reemission_nlte(self, fetch=True):
+        """The per-grain re-emission tables on the device (``mcgpu_init_reemission_nlte``); returns
+        ``(log_E_em_1grain [n_T, n_grains], kdB_dT_1grain_nLTE_CDF [n_T, n_grains, n_lambda])`` when ``fetch``."""
+        m, ng = self.model, int(self.nlte["n_grains"])
+        nT, nl = m.tab_Temp.size, m.n_lambda
+        lE = np.zeros((nT, ng), np.float64) if fetch else None
+        cdf = np.zeros((nT, ng, nl), np.float64) if fetch else None
+        self._chk(self.lib.mcgpu_init_reemission_nlte(
+            self.ctx, _p(_a(m.lam, np.float64), C.c_double), _p(_a(m.delta_lam, np.float64), C.c_double),
+            _p(lE, C.c_double) if fetch else None, _p(cdf, C.c_double) if fetch else None), "mcgpu_init_reemission_nlte")
+        return lE, cdf
+
+    def set_J0(self, J0):
+        """``J0 [n_lambda, n_cells]`` (radiation_field.f90:27) or None (zeros)."""
+        self._chk(self.lib.mcgpu_set_J0(self.ctx, None if J0 is None else _p(_a(J0, np.float64), C.c_double)), "mcgpu_set_J0")
+
+    def temp_finale_nlte(self, xJ_abs=None):
+        """``Temp_finale_nLTE``: ``Tdust_1grain [n_cells, n_grains]`` from ``xJ_abs [n_lambda, n_cells]`` (None: the device's)."""
+        T = np.zeros((self.model.n_cells, int(self.nlte["n_grains"])), np.float32)
+        xp = None if xJ_abs is None else _p(_a(xJ_abs, np.float64), C.c_double)
+        self._chk(self.lib.mcgpu_temp_finale_nlte(self.ctx, xp, _p(T, C.c_float)), "mcgpu_temp_finale_nlte")
+        return T
+
+    def set_Tdust_1grain(self, Tdust_1grain, grain_density=None):
+        """The lRE_nLTE term of ``repartition_energie`` (None: off again)."""
+        if Tdust_1grain is None:
+            self._chk(self.lib.mcgpu_set_Tdust_1grain(self.ctx, None, None), "mcgpu_set_Tdust_1grain")
+            return
+        dens = self.nlte["grain_density"] if grain_density is None else grain_density
+        self._chk(self.lib.mcgpu_set_Tdust_1grain(self.ctx, _p(_a(Tdust_1grain, np.float32), C.c_float),
+                                                  _p(_a(dens, np.float64), C.c_double)), "mcgpu_set_Tdust_1grain")
+
+    def probe_reemission_nlte(self, icell, lambda0, rand1, rand2):
+        """One re-emission event per case on ``J0`` (``mcgpu_probe_reemission_nlte``): ``(k, T_int, Temp, lambda)``."""
+        ic, l0 = _a(icell, np.int32), _a(lambda0, np.int32)
+        r1, r2 = _a(rand1, np.float32), _a(rand2, np.float32)
+        n = ic.size
+        k, Ti, lam = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        Temp = np.zeros(n, np.float64)
+        self._chk(self.lib.mcgpu_probe_reemission_nlte(
+            self.ctx, C.c_int(n), _p(ic, C.c_int), _p(l0, C.c_int), _p(r1, C.c_float), _p(r2, C.c_float),
+            _p(k, C.c_int), _p(Ti, C.c_int), _p(Temp, C.c_double), _p(lam, C.c_int)), "mcgpu_probe_reemission_nlte")
+        return k, Ti, Temp, lam
 
     def set_mrw(self, mrw):
         """Tables of the modified random walk (``mcfost_amd.host.model.init_mrw``); ``None`` switches it off."""

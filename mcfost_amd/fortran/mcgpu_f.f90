@@ -99,7 +99,8 @@ module mcgpu_f
        mcgpu_set_E_prior, mcgpu_multi_create, mcgpu_multi_destroy, mcgpu_multi_size, mcgpu_multi_ctx, mcgpu_multi_run_thermal, mcgpu_multi_run_mono, mcgpu_multi_run_sed, mcgpu_multi_rccl_ranks, mcgpu_multi_create_ex, mcgpu_multi_reductions, &
        mcgpu_counters_to_accum, mcgpu_counters_from_accum, mcgpu_temp_approx_diffusion_vertical, mcgpu_set_mrw, mcgpu_set_mrw_exit_spectrum, mcgpu_fetch_radiation_field, &
        mcgpu_build_ksca_CDF, mcgpu_voronoi_tesselation, &
-       mcgpu_set_variable_dust, mcgpu_rt1_stars_map_sed, mcgpu_define_dark_zone, mcgpu_init_reemission, mcgpu_init_reemission_ex, mcgpu_repartition_energie, mcgpu_opacity, mcgpu_set_variable_dust_s11, mcgpu_set_scattering_method1, mcgpu_set_rt2, mcgpu_fetch_I_spec, mcgpu_rt1_stars_map_image, mcgpu_set_I_spec, mcgpu_rt2_source, mcgpu_rt2_dust_map, mcgpu_rt2_image, mcgpu_tau_maps
+       mcgpu_set_variable_dust, mcgpu_rt1_stars_map_sed, mcgpu_define_dark_zone, mcgpu_init_reemission, mcgpu_init_reemission_ex, mcgpu_repartition_energie, mcgpu_opacity, mcgpu_set_variable_dust_s11, mcgpu_set_scattering_method1, mcgpu_set_rt2, mcgpu_fetch_I_spec, mcgpu_rt1_stars_map_image, mcgpu_set_I_spec, mcgpu_rt2_source, mcgpu_rt2_dust_map, mcgpu_rt2_image, mcgpu_tau_maps, &
+       mcgpu_set_nlte, mcgpu_init_reemission_nlte, mcgpu_set_J0, mcgpu_temp_finale_nlte, mcgpu_set_Tdust_1grain, mcgpu_probe_reemission_nlte
 
   interface
      integer(c_int) function mcgpu_create(device, ctx) bind(C, name="mcgpu_create")
@@ -670,6 +671,60 @@ module mcgpu_f
        real(c_double), intent(in) :: E_abs(*)
        real(c_float), intent(out) :: Tdust(*)
      end function mcgpu_temp_finale
+
+     ! Grains in radiative equilibrium out of LTE (lRE_nLTE; include/mcgpu.h).  The module arrays as they are, restricted
+     ! to grain_RE_nLTE_start:grain_RE_nLTE_end; optional ones as c_loc(array) or c_null_ptr.
+     integer(c_int) function mcgpu_set_nlte(ctx, n_grains_nlte, n_grains_nRE, C_abs_norm, kabs_nLTE_CDF, Proba_abs_RE_LTE, &
+          grain_density, log_E_em_1grain, kdB_dT_1grain_nLTE_CDF) bind(C, name="mcgpu_set_nlte")
+       import :: c_int, c_ptr, c_double, c_float
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: n_grains_nlte, n_grains_nRE
+       real(c_float), intent(in) :: C_abs_norm(*)        ! (k, lambda)
+       real(c_double), intent(in) :: kabs_nLTE_CDF(*)    ! (0:n, lambda) of the single dust class
+       type(c_ptr), value :: Proba_abs_RE_LTE            ! (n_cells, lambda) real(dp), or null: lonly_nLTE
+       type(c_ptr), value :: grain_density               ! (k, n_cells) real(dp): dust_density_o_n_grains * n_grains, or null
+       type(c_ptr), value :: log_E_em_1grain             ! (k, T) real(dp), or null: mcgpu_init_reemission_nlte
+       type(c_ptr), value :: kdB_dT_1grain_nLTE_CDF      ! (lambda, k, T) real(dp), or null
+     end function mcgpu_set_nlte
+
+     integer(c_int) function mcgpu_init_reemission_nlte(ctx, tab_lambda, tab_delta_lambda, log_E_em_1grain, &
+          kdB_dT_1grain_nLTE_CDF) bind(C, name="mcgpu_init_reemission_nlte")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(in) :: tab_lambda(*), tab_delta_lambda(*)
+       type(c_ptr), value :: log_E_em_1grain, kdB_dT_1grain_nLTE_CDF   ! out, real(dp), or null
+     end function mcgpu_init_reemission_nlte
+
+     integer(c_int) function mcgpu_set_J0(ctx, J0) bind(C, name="mcgpu_set_J0")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       type(c_ptr), value :: J0                          ! (n_cells, n_lambda) real(dp), or null: zeros
+     end function mcgpu_set_J0
+
+     integer(c_int) function mcgpu_temp_finale_nlte(ctx, xJ_abs, Tdust_1grain) bind(C, name="mcgpu_temp_finale_nlte")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: ctx
+       type(c_ptr), value :: xJ_abs                      ! (n_cells, n_lambda) real(dp) summed over threads, or null: the device's
+       real(c_float), intent(out) :: Tdust_1grain(*)     ! (k, n_cells)
+     end function mcgpu_temp_finale_nlte
+
+     integer(c_int) function mcgpu_set_Tdust_1grain(ctx, Tdust_1grain, grain_density) bind(C, name="mcgpu_set_Tdust_1grain")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       type(c_ptr), value :: Tdust_1grain                ! (k, n_cells) real, or null: off again
+       type(c_ptr), value :: grain_density               ! (k, n_cells) real(dp)
+     end function mcgpu_set_Tdust_1grain
+
+     integer(c_int) function mcgpu_probe_reemission_nlte(ctx, n, icell, lambda0, rand1, rand2, k_out, T_int_out, Temp_out, &
+          lambda_out) bind(C, name="mcgpu_probe_reemission_nlte")
+       import :: c_int, c_ptr, c_double, c_float
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: n
+       integer(c_int), intent(in) :: icell(*), lambda0(*)
+       real(c_float), intent(in) :: rand1(*), rand2(*)
+       integer(c_int), intent(out) :: k_out(*), T_int_out(*), lambda_out(*)
+       real(c_double), intent(out) :: Temp_out(*)
+     end function mcgpu_probe_reemission_nlte
   end interface
 
 contains

@@ -597,6 +597,94 @@ def init_reemission(lam, delta_lam, tab_Temp, kappa_abs_LTE):
     return log_Qcool, cdf
 
 
+def planck_tables(lam, delta_lam, tab_Temp, real_literal=False):
+    """``B(lambda, T)`` and ``dB_dT(lambda, T)`` of init_reemission (thermal_emission.f90:431-452), ``[n_T, n_lambda]``.
+    ``real_literal``: micron to metre with the reference's default-real 1.e-6 (:439-440) instead of the double that
+    ``init_reemission`` above takes (2.5e-8 on the wavelengths)."""
+    mum = float(f32(1.0e-6)) if real_literal else 1.0e-6
+    wl = np.asarray(lam, f64) * mum
+    dwl = np.asarray(delta_lam, f64) * mum
+    n_T = tab_Temp.size
+    B = np.zeros((n_T, wl.size), f64)
+    dB = np.zeros((n_T, wl.size), f64)
+    for t in range(n_T):
+        cst_wl = (THERMAL_CONST / float(tab_Temp[t])) / wl
+        ok = cst_wl < 500.0
+        ce = np.exp(np.where(ok, cst_wl, 1.0))
+        b = np.where(ok, 1.0 / ((wl ** 5) * (ce - 1.0)) * dwl, 0.0)
+        B[t] = b
+        dB[t] = np.where(ok, b * cst_wl * ce / (ce - 1.0), 0.0)
+    return B, dB
+
+
+def init_nlte(m: "Model", grains: dict, dens, nlte_range, C_abs_norm=None, real_literal=False):
+    """Tables of the grains in radiative equilibrium out of LTE (lRE_nLTE) for one dust class -- an input builder, like
+    ``init_reemission``: grains ``nlte_range = (first, last)`` (1-based, inclusive) of ``synthetic_grains`` are non-LTE, the
+    others LTE; ``dens [n_grains]`` (or ``[1, n_grains]``) is ``dust_density_o_n_grains`` of the single class
+    (``settled_grain_density(per_cell=False, n_classes=1)``), the cells' dust is the model's ``kappa_factor``.
+    Arrays are C-ordered with the Fortran first index last:
+      C_abs_norm [n_lambda, n]                 dust_prop.f90:636 (default real)
+      kabs_nLTE_CDF [n_lambda, n + 1]          dust_prop.f90:931-943
+      Proba_abs_RE_LTE [n_lambda, n_cells]     dust_prop.f90:916-921; None when every grain is non-LTE (lonly_nLTE)
+      grain_density [n_cells, n]               dust_density_o_n_grains(k, icell) n_grains(k)
+      log_E_em_1grain [n_T, n], kdB_dT_1grain_nLTE_CDF [n_T, n, n_lambda]   thermal_emission.f90:552-582
+      J0 [n_lambda, n_cells]                   volume B(lambda, T_min) cst_E (thermal_emission.f90:508-512)
+    ``C_abs_norm``: given instead of formed from ``grains["C_abs"]`` (a grain with a prescribed cross section).
+    And, for the context's LTE branch, the LTE grains' share of the model's absorption: ``kappa_abs_LTE [n_lambda]`` with its
+    ``log_Qcool`` / ``kdB_dT_CDF`` (the model's own when there is no LTE grain: the branch is never taken)."""
+    k0, k1 = int(nlte_range[0]), int(nlte_range[1])
+    ng_tot = int(grains["n_grains"])
+    assert 1 <= k0 <= k1 <= ng_tot
+    n = k1 - k0 + 1
+    nl, n_T, n_cells = m.n_lambda, m.tab_Temp.size, m.n_cells
+    C_abs = np.asarray(grains["C_abs"], f32)                                   # [nl, ng_tot]
+    density = np.asarray(dens, f64).reshape(-1)[:ng_tot] * np.asarray(grains["n_grains_k"], f64)
+    if C_abs_norm is None:
+        C_abs_norm = (C_abs[:, k0 - 1:k1].astype(f64) * AU_TO_CM * MUM_TO_CM ** 2).astype(f32)
+    C_abs_norm = np.ascontiguousarray(C_abs_norm, f32).reshape(nl, n)
+    kcdf = np.zeros((nl, n + 1), f64)
+    for k in range(1, n + 1):
+        kcdf[:, k] = kcdf[:, k - 1] + C_abs[:, k0 - 2 + k].astype(f64) * density[k0 - 2 + k]
+    tot = kcdf[:, n].copy()
+    ok = tot > TINY_REAL
+    kcdf[ok] = kcdf[ok] / tot[ok, None]
+    lte = np.ones(ng_tot, bool)
+    lte[k0 - 1:k1] = False
+    proba = None
+    kabs_lte = np.asarray(m.kappa_abs_LTE, f64).copy()
+    lq, cdf_lte = m.log_Qcool, m.kdB_dT_CDF
+    if lte.any():
+        k_abs_LTE = np.zeros(nl, f64)
+        for k in np.nonzero(lte)[0]:
+            k_abs_LTE = k_abs_LTE + C_abs[:, k].astype(f64) * density[k]
+        k_abs_RE = k_abs_LTE.copy()
+        for k in range(k0 - 1, k1):
+            k_abs_RE = k_abs_RE + C_abs[:, k].astype(f64) * density[k]
+        row = np.where(k_abs_RE > TINY_DP, k_abs_LTE / np.where(k_abs_RE > TINY_DP, k_abs_RE, 1.0), 1.0)
+        proba = np.ascontiguousarray(np.broadcast_to(row[:, None], (nl, n_cells)), f64).copy()
+        proba[:, np.asarray(m.kappa_factor, f64)[:n_cells] <= 0.0] = 1.0       # (empty cells, :920)
+        kabs_lte = kabs_lte * row
+        lq, cdf_lte = init_reemission(m.lam, m.delta_lam, m.tab_Temp, kabs_lte)
+    B, dB = planck_tables(m.lam, m.delta_lam, m.tab_Temp, real_literal)
+    cst_E = 2.0 * HP * C_LIGHT ** 2 * (4.0 * PI)
+    Cn = C_abs_norm.astype(f64)                                                # [nl, n]
+    integ = np.zeros((n_T, n), f64)
+    integ3 = np.zeros((n_T, n, nl), f64)
+    for l in range(nl):                                                        # the reference's order over lambda
+        integ = integ + Cn[l][None, :] * B[:, l][:, None]
+        if l > 0:
+            integ3[:, :, l] = integ3[:, :, l - 1] + Cn[l][None, :] * dB[:, l][:, None]
+    lE = np.where(integ > TINY_DP, np.log(np.where(integ > TINY_DP, integ, 1.0) * cst_E), -1000.0)
+    last = integ3[:, :, nl - 1]
+    cdf = np.where((last > TINY_DP)[:, :, None], integ3 / np.where(last > TINY_DP, last, 1.0)[:, :, None], 0.0)
+    vol = np.asarray(m.grid["volume"], f64)[:n_cells]
+    J0 = np.ascontiguousarray((B[0] * cst_E)[:, None] * vol[None, :])
+    gd = np.ascontiguousarray(np.asarray(m.kappa_factor, f64)[:n_cells, None] * density[None, k0 - 1:k1])
+    return dict(n_grains=n, nlte_range=(k0, k1), C_abs_norm=C_abs_norm, kabs_nLTE_CDF=kcdf, Proba_abs_RE_LTE=proba,
+                grain_density=gd, log_E_em_1grain=np.ascontiguousarray(lE), kdB_dT_1grain_nLTE_CDF=np.ascontiguousarray(cdf),
+                J0=J0, kappa_abs_LTE=kabs_lte, log_Qcool=lq, kdB_dT_CDF=cdf_lte)
+
+
 # --------------------------------------------------------------------------
 # The assembled model
 # --------------------------------------------------------------------------

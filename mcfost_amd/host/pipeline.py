@@ -36,6 +36,20 @@ class EngineBackend:
     def temp_approx_diffusion_vertical(self, Tdust, ri_in, ri_out, zj_sup):
         return self.e.temp_approx_diffusion_vertical(Tdust, ri_in, ri_out, zj_sup)[0]
 
+    def nlte_grains(self):
+        """None: LTE grains only; "only": non-LTE grains alone (lonly_nLTE); "mixed": both"""
+        nl = getattr(self.e, "nlte", None)
+        return None if nl is None else ("only" if nl.get("Proba_abs_RE_LTE") is None else "mixed")
+
+    def temp_finale_nlte(self):
+        """Temp_finale_nLTE after a temperature step with grains out of LTE (Engine.set_nlte): Tdust_1grain [n_cells, n_grains],
+        handed on to the SED step's repartition_energie (its lRE_nLTE term); None without such grains."""
+        if getattr(self.e, "nlte", None) is None:
+            return None
+        T1 = self.e.temp_finale_nlte()
+        self.e.set_Tdust_1grain(T1)
+        return T1
+
     def repartition_energie(self, lam, Tdust):
         """repartition_energie(lam) on the device (mcgpu_repartition_energie): the wavelength's emission tables stay in
         HBM for the run_mono that follows; returns E_disk(lam)."""
@@ -85,9 +99,19 @@ def temperature_and_sed(backend, m, n_thermal, n_photons_lambda, lambdas=None, s
     (packets sent per wavelength in the SED step), ``sed_rt`` (n_lambda, nRT, N_type_flux; dust only) and the
     wall time of each stage."""
     t = {}
+    nlte = backend.nlte_grains() if hasattr(backend, "nlte_grains") else None
+    if nlte is not None and ray_tracing:   # (said before anything runs or changes the context)
+        raise NotImplementedError("ray-traced SED with grains out of LTE: the ray tracer's thermal emissivity has no per-grain "
+                                  "term (dust_ray_tracing.f90:860-890); run with ray_tracing=False")
     t0 = time.perf_counter()
     th = backend.run_thermal(int(n_thermal), seed)
     Tdust = backend.temp_finale(th["E_abs"])
+    # grains out of LTE (lRE_nLTE): their own temperatures, which the SED step's emission tables then hold
+    Tdust_1grain = backend.temp_finale_nlte() if nlte is not None else None
+    if nlte == "only":
+        # no LTE grain: the reference's kappa_abs_LTE is 0 and the LTE term of repartition_energie with it; the context's
+        # kappa_abs_LTE is the whole dust's here (the deposits of E_abs), so the LTE term is switched off by its temperature
+        Tdust = np.zeros_like(Tdust)
     t["thermal"] = time.perf_counter() - t0
     if diff_approx is not None:  # ldiff_approx with a dark zone: dust_transfer.f90:316 / :659
         t0 = time.perf_counter()
@@ -130,8 +154,11 @@ def temperature_and_sed(backend, m, n_thermal, n_photons_lambda, lambdas=None, s
         for lam, v in E_disk.items():
             Ed[lam - 1] = v
         m.extra["E_disk"] = Ed
-    return dict(Tdust=Tdust, sed_mc=sed, n_sent=n_sent, sed_rt=sed_rt, sed_rt_stars=sed_rt_stars, seconds=t,
-                thermal_counters=th["counters"], E_disk=E_disk, sed_crossings=sed_crossings)
+    out = dict(Tdust=Tdust, sed_mc=sed, n_sent=n_sent, sed_rt=sed_rt, sed_rt_stars=sed_rt_stars, seconds=t,
+               thermal_counters=th["counters"], E_disk=E_disk, sed_crossings=sed_crossings)
+    if Tdust_1grain is not None:
+        out["Tdust_1grain"] = Tdust_1grain
+    return out
 
 
 def stars_flux_factor(m, lam):
