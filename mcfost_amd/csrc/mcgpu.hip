@@ -74,12 +74,63 @@ constexpr int CNT_SLOTS = 24;  // d_counters: the counters, the longest packet's
 static_assert(MCGPU_N_COUNTERS <= WORK_SLOT, "counter buffer layout");
 static_assert(MCGPU_N_COUNTERS == TAIL_N_COUNTERS, "mc_tail.hip.h counts the same events");
 
+// (internal types: hidden, so that their instantiations stay out of the library's dynamic symbols)
+#pragma GCC visibility push(hidden)
+
+// A device array and its owner: move-only, freed with its scope (a call's temporaries) or with the context (its members).
+// The structures handed to kernels by value (DevModel, RunArgs, BinLog, ...) hold plain pointers filled from these: views.
+template <typename Tp>
+struct DevArr {
+  Tp* p = nullptr;
+  size_t n = 0;   // values allocated
+  DevArr() = default;
+  DevArr(DevArr&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevArr& operator=(DevArr&& o) noexcept { if (this != &o) { reset(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+  ~DevArr() { reset(); }
+  operator Tp*() const { return p; }
+  void reset() { if (p) hipFree(p); p = nullptr; n = 0; }
+  // exactly n_new values: nothing happens when that is what there is; otherwise the old array goes first
+  hipError_t resize(size_t n_new) {
+    if (p && n == n_new) return hipSuccess;
+    reset();
+    const hipError_t e = hipMalloc((void**)&p, (n_new ? n_new : 1) * sizeof(Tp));
+    if (e == hipSuccess) n = n_new; else p = nullptr;
+    return e;
+  }
+  hipError_t reserve(size_t n_min) { return n >= n_min && (p || !n_min) ? hipSuccess : resize(n_min); }   // at least n_min values
+  hipError_t put(const Tp* h, size_t k) { return hipMemcpy(p, h, k * sizeof(Tp), hipMemcpyHostToDevice); }
+  hipError_t get(Tp* h, size_t k) const { return hipMemcpy(h, p, k * sizeof(Tp), hipMemcpyDeviceToHost); }
+};
+
+// ... and the same for a stream, an event and the pinned arena
+template <typename H, hipError_t (*Destroy)(H)>
+struct Owned {
+  H h = nullptr;
+  Owned() = default;
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() { reset(); }
+  operator H() const { return h; }
+  void reset() { if (h) Destroy(h); h = nullptr; }
+};
+static inline hipError_t free_pinned(char* p) { return hipHostFree(p); }
+using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
+using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
+using OwnedPinned = Owned<char*, free_pinned>;
+
+// Members are destroyed in reverse order of declaration: the streams, the events and the arena come first, so that every
+// device array has gone (hipFree waits for the device) before the streams its launches ran on.  Whoever deletes a context
+// makes its device current first.
 struct mcgpu_ctx {
   int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t ev_tail = nullptr;     // recorded in front of k_tail: the launch's tail is [ev_tail, ev1]
+  OwnedStream own_stream;
+  hipStream_t stream = nullptr;     // own_stream, or the caller's (mcgpu_set_stream)
+  OwnedEvent ev0, ev1;
+  OwnedEvent ev_tail;               // recorded in front of k_tail: the launch's tail is [ev_tail, ev1]
+  OwnedStream side_stream;          // copies the tables while k_tail runs
+  OwnedEvent ev_side_in, ev_side_out;
+  OwnedPinned h_arena;              // pinned: the launch's table copies, accumulators, counters and records
+  size_t h_arena_bytes = 0;
   bool tail_launched = false;
   hipDeviceProp_t prop;
   std::string err;
@@ -90,9 +141,9 @@ struct mcgpu_ctx {
   bool pending_single = false, pending_classes = false;  // ... which of the two sets
   int lsepar_pola = 0;
   int mrw_classes = 0;              // the number of classes the random walk's tables were set for
-  double2* d_vkk = nullptr;         // the variable-dust role kernel's per-cell opacity pairs (built at the first launch)
+  DevArr<double2> d_vkk;            // the variable-dust role kernel's per-cell opacity pairs (built at the first launch)
   bool vkk_valid = false;
-  std::vector<void*> opacity_allocs;  // the per-class tables mcgpu_opacity built (freed by the next call)
+  std::vector<DevArr<char>> opacity_allocs;  // the per-class tables mcgpu_opacity built (freed by the next call)
   float T_min = 1.0f;
   // mcgpu_set_option
   int opt_deposit = 0;      // 0 = automatic, 1 = HBM atomics, 2 = LDS-private grid / deposit cache, 3 = binned deposits
@@ -102,28 +153,25 @@ struct mcgpu_ctx {
   std::vector<double> h_r_lim;     // host copy of r_lim (cylindrical grids): the optical-thickness estimate below
   double tau_midplane = -1.0;      // radial optical depth of the midplane at the most opaque wavelength (-1: unknown)
   double last_inter_pp = -1.0;     // interactions per packet of the context's last completed thermal launch (-1: none yet)
-  unsigned int* d_tail_next = nullptr;  // the tail kernel's work counter
+  DevArr<unsigned int> d_tail_next;     // the tail kernel's work counter
   // the tail's last packets on the host (mc_tail.hip.h "The last packets on the host", host_tail.cpp)
   int opt_tail_where = 0;        // 0 = automatic (the host), 1 = k_tail finishes every packet, 2 = the host finishes the last ones
   int opt_host_threads = 0;      // host threads of a tail (0: the machine's, shared among its GPUs; at most 32)
   int opt_tail_host_max = 0;     // packets k_tail leaves to the host (0: 8 per host thread)
-  unsigned int* d_tail_ctl = nullptr;   // [0] packets k_tail has finished, [1] records it has written to d_tail_out
-  void* d_tail_out = nullptr;           // [tail_out_cap] records for the host
-  unsigned int tail_out_cap = 0;
-  char* h_arena = nullptr;              // pinned: the launch's table copies, accumulators, counters and records
-  size_t h_arena_bytes = 0;
-  hipStream_t side_stream = nullptr;    // copies the tables while k_tail runs
-  hipEvent_t ev_side_in = nullptr, ev_side_out = nullptr;
+  DevArr<unsigned int> d_tail_ctl;      // [0] packets k_tail has finished, [1] records it has written to d_tail_out
+  DevArr<char> d_tail_out;              // records (Rec<true>) for the host
   bool tail_on_host = false;            // the last thermal launch handed its last packets to the host
   // what the last host tail did (written by its callback; read after a synchronisation)
   double host_tail_ms = 0.0;
   unsigned int host_tail_packets = 0;
   int host_tail_threads = 0;
   unsigned long long host_tail_events = 0;
-  // binned deposits (mc_binned.hip.h): the log and its plan
+  // binned deposits (mc_binned.hip.h): the log's arrays, the view of them the kernels take, and its plan
+  DevArr<unsigned int> d_bin_keys, d_bin_count, d_bin_off, d_bin_cap;
+  DevArr<double> d_bin_vals;
+  DevArr<unsigned long long> d_bin_stats;
+  DevArr<double> d_bin_want;     // [n_buckets] scratch of k_plan_bins
   BinLog bin{};
-  unsigned int *d_bin_off = nullptr, *d_bin_cap = nullptr;
-  double* d_bin_want = nullptr;  // [n_buckets] scratch of k_plan_bins
   unsigned long long bin_total_blocks = 0;
   bool bin_log_capped = false;      // the log was cut to a share of the free memory (asking again would not get more)
   int bin_max_parts = 0;
@@ -131,9 +179,8 @@ struct mcgpu_ctx {
   int bin_chunks = 0;               // chunks of the last launch
   double accum_packets = 0.0;       // packets whose deposits the accumulators hold (across accumulate-launches)
   // packets a chunk leaves unfinished (mc_roles.hip.h, "Chunks without tails"): two record buffers used in turns
-  void* d_carry[2] = {nullptr, nullptr};
-  unsigned int* d_carry_n = nullptr;  // [2]
-  size_t carry_cap = 0;               // records per buffer
+  DevArr<char> d_carry[2];          // records (Rec<true>), as many in each
+  DevArr<unsigned int> d_carry_n;   // [2]
   int opt_schedule = 0;     // 0 = automatic (waves with roles where the queues fit), 1 = single-role kernel
   int opt_speculation = 1;  // SED mode: commit most of every stream before the scout pass
   int opt_cache_log_slots = 13;  // Voronoi deposit cache: 2^13 slots = 96 KB of LDS
@@ -141,81 +188,76 @@ struct mcgpu_ctx {
   int opt_pool_log_rec = 12;     // Voronoi pool schedule: 2^12 packet records per workgroup (mc_voronoi_pool.hip.h)
   int opt_nlte_stats = 0;        // 1: a non-LTE launch counts the events its waves serve (mcgpu_get_info "nlte_events" / "nlte_visits")
   int opt_radiation_field = 0;   // bit 0: xN_abs, bit 1: xJ_abs (thermal step; radiation_field.f90:54-55)
-  unsigned long long* d_xN = nullptr;  // [n_cells] (64-bit: a hot cell passes 2^32 segments within one 1e9-packet run)
-  double* d_xJ = nullptr;        // (n_cells, n_lambda)
-  std::vector<void*> allocs;   // every table buffer (freed in destroy)
-  // per-setter buffers that may be replaced
+  DevArr<unsigned long long> d_xN;   // [n_cells] (64-bit: a hot cell passes 2^32 segments within one 1e9-packet run)
+  DevArr<double> d_xJ;           // (n_cells, n_lambda)
+  std::vector<DevArr<char>> allocs;   // every table buffer (upload(); freed with the context)
+  // views of tables in `allocs` that a later setter patches
   int *d_cmi = nullptr, *d_cmj = nullptr, *d_cmk = nullptr;
   float* d_tab_Temp = nullptr;
   // accumulators: [E_abs | sed | n_sent | counters as doubles (mcgpu_counters_to_accum)]
-  double* d_accum = nullptr;
-  size_t n_accum = 0;
-  unsigned long long* d_counters = nullptr;  // [CNT_SLOTS]: MCGPU_N_COUNTERS counters, pad, the work counter at WORK_SLOT
-  int* d_err = nullptr;
-  double* d_E_prior = nullptr;
+  DevArr<double> d_accum;
+  DevArr<unsigned long long> d_counters;  // [CNT_SLOTS]: MCGPU_N_COUNTERS counters, pad, the work counter at WORK_SLOT
+  DevArr<int> d_err;
+  DevArr<double> d_E_prior;      // [n_cells]
   bool launched = false;
   // SED mode (mc_mono.hip.h)
   bool have_rt1 = false;
   int RT_n_incl = 0, RT_n_az = 0, n_az_rt = 0, n_theta_rt = 0, N_type_flux = 0, lsepar_contrib = 0, n_lambda_pos = 0;
   const double *d_rt_u = nullptr, *d_rt_v = nullptr, *d_rt_w = nullptr;
   const float* d_tab_s11 = nullptr;
-  double* d_xI = nullptr;
+  DevArr<double> d_xI;              // xi_dev_bytes() bytes, whichever type they hold
   bool have_rt2 = false;            // ray tracing method 2 (mcgpu_set_rt2): I_spec, I_spec_star
   int n_theta_I = 0, n_phi_I = 0, rt2_N_type_flux = 0, rt2_contrib = 0;
-  double *d_I_spec = nullptr, *d_I_spec_star = nullptr;
+  DevArr<double> d_I_spec, d_I_spec_star;
   // the source function of the last mcgpu_rt2_source, resident for mcgpu_rt2_dust_map / mcgpu_rt2_image
-  float *d_eps2 = nullptr, *d_eps2_star = nullptr;
-  double* d_rt2_zgrid = nullptr;
+  DevArr<float> d_eps2, d_eps2_star;
+  DevArr<double> d_rt2_zgrid;
   int rt2_src_ibin = 0, rt2_src_lambda = 0, rt2_src_nang = 0, rt2_src_nang_star = 0;
-  size_t n_xI = 0;
+  size_t n_xI = 0;   // elements of the reference's xI_scatt that d_xI stands for (0: none)
   int xI_bytes = 8;  // accumulator type of xI_scatt on the device: 8 = FP64 (default), 4 = default real (mcgpu_set_xI_precision)
-  double* d_prob_E = nullptr;               // prob_E_cell(0:n_cells) of the current wavelength
+  DevArr<double> d_prob_E;                  // prob_E_cell(0:n_cells) of the current wavelength
   int prob_E_lambda = 0;                    // the wavelength mcgpu_repartition_energie left in d_prob_E (0: none)
   double prob_E_fstar = 0.0, prob_E_fdisk = 0.0;
-  unsigned long long* d_mono_u64 = nullptr; // [5 * n_chunks + 1]: need | sent | item_base(+1) | start | hit_count
-  int* d_mono_i32 = nullptr;                // [2 * n_chunks]: active | done
-  int mono_chunks = 0;
-  unsigned char* d_hits = nullptr;
-  size_t hits_cap = 0;
+  DevArr<unsigned long long> d_mono_u64;    // [5 * n_chunks + 1]: need | sent | item_base(+1) | start | hit_count
+  DevArr<int> d_mono_i32;                   // [2 * n_chunks]: active | done
+  DevArr<unsigned char> d_hits;
   // the SED commit pass's deposit log (mc_mono.hip.h "The deposits as a log", mc_xilog.hip.h)
   int opt_xi_log = 1;               // 1 (default): default-real xI_scatt of one dust class on a cylindrical grid is summed from a log
                                     // where a wavelength's flights are long enough for that to pay; 0: atomics; 2: the log always
-  unsigned int* d_xlog_keys[2] = {nullptr, nullptr};       // [0]: the launch's log; [1]: the sorted copy
-  unsigned long long* d_xlog_vals[2] = {nullptr, nullptr};
-  float* d_xlog_rows = nullptr;
-  unsigned long long* d_xlog_ctl = nullptr;     // [0] records, [1] flights the launch's waves reserved
-  size_t xlog_cap = 0, xlog_rows_cap = 0, xlog_row_floats = 0;
-  void* d_xlog_temp = nullptr;
-  size_t xlog_temp_bytes = 0;
+  DevArr<unsigned int> d_xlog_keys[2];          // [0]: the launch's log; [1]: the sorted copy
+  DevArr<unsigned long long> d_xlog_vals[2];
+  DevArr<float> d_xlog_rows;                    // [rows][xlog_row_floats]
+  DevArr<unsigned long long> d_xlog_ctl;        // [0] records, [1] flights the launch's waves reserved
+  size_t xlog_row_floats = 0;
+  DevArr<char> d_xlog_temp;
   int xlog_chunks = 0;              // launches of the last wavelength's commit passes
   unsigned long long xlog_records = 0, xlog_flights = 0;   // ... and what they logged
   // Voronoi grid (mc_voronoi.hip.h)
   bool voro = false;
   VoroGrid V;
   std::vector<VoroCell> h_cells;  // host copy: kappa_factor is patched in by mcgpu_set_opacity
-  VoroCell* d_cells = nullptr;
-  void* d_pool = nullptr;          // the pool schedule's packet records (mc_voronoi_pool.hip.h), [blocks][1 << log_rec] x 128 B
-  size_t pool_bytes = 0;
-  VpBlob* d_pool_blob = nullptr;   // ... and the copy of a launch's arguments its emission phase reads
+  VoroCell* d_cells = nullptr;    // (a table in `allocs`)
+  DevArr<char> d_pool;             // the pool schedule's packet records (mc_voronoi_pool.hip.h), [blocks][1 << log_rec] x 128 B
+  DevArr<VpBlob> d_pool_blob;      // ... and the copy of a launch's arguments its emission phase reads
   VpBlob h_pool_blob;
   // grains out of LTE (mc_nlte.hip.h; mcgpu_set_nlte): n_grains = 0: off
   struct {
     int n_grains = 0;
     bool mixed = false;            // Proba_abs_RE_LTE was given (LTE grains next to the non-LTE ones)
     bool tables_pending = false;   // log_E_em_1grain / the CDF were left to mcgpu_init_reemission_nlte
-    float* d_Cabs = nullptr;
-    double *d_kcdf = nullptr, *d_proba = nullptr, *d_dens = nullptr, *d_lE = nullptr, *d_cdf = nullptr;
-    double *d_J0 = nullptr, *d_xJ = nullptr;   // [n_cells][ldJ]
-    unsigned long long* d_stats = nullptr;     // [2] events served / wave visits of the last launch
+    DevArr<float> d_Cabs;
+    DevArr<double> d_kcdf, d_proba, d_dens, d_lE, d_cdf;
+    DevArr<double> d_J0, d_xJ;     // [n_cells][ldJ]
+    DevArr<unsigned long long> d_stats;        // [2] events served / wave visits of the last launch
     bool xJ_last = false;          // the last thermal launch kept xJ_abs in d_xJ (mcgpu_fetch_radiation_field)
     // mcgpu_set_Tdust_1grain: the lRE_nLTE term of mcgpu_repartition_energie
-    float* d_T1 = nullptr;         // [n_cells][n_grains]
-    double* d_T1_dens = nullptr;   // [n_cells][n_grains]
+    DevArr<float> d_T1;            // [n_cells][n_grains]
+    DevArr<double> d_T1_dens;      // [n_cells][n_grains]
     int T1_grains = 0;
     int dim_lambda = 0, dim_T = 0, dim_cells = 0;   // the model's sizes when the tables were set
-    size_t J0_n = 0, xJ_n = 0;                      // doubles of d_J0 / d_xJ
   } nl;
 };
+#pragma GCC visibility pop
 
 static void bin_release(mcgpu_ctx* ctx);
 static void nlte_release(mcgpu_ctx* ctx, bool all);
@@ -234,10 +276,11 @@ static int tail_threshold(const mcgpu_ctx* ctx);
 // n values from the host into a new device array of max(n, n_alloc) values (the rest zeroed)
 template <typename Tp>
 static int upload(mcgpu_ctx* ctx, const Tp* host, size_t n, const Tp** dev_out, size_t n_alloc = 0) {
-  Tp* d = nullptr;
   const size_t na = n_alloc > n ? n_alloc : n;
-  HIPCHK(hipMalloc((void**)&d, (na ? na : 1) * sizeof(Tp)));
-  ctx->allocs.push_back(d);
+  DevArr<char> a;
+  HIPCHK(a.resize(na * sizeof(Tp)));
+  Tp* d = reinterpret_cast<Tp*>(a.p);
+  ctx->allocs.push_back(std::move(a));
   if (na > n) HIPCHK(hipMemset(d, 0, na * sizeof(Tp)));
   if (n) HIPCHK(hipMemcpy(d, host, n * sizeof(Tp), hipMemcpyHostToDevice));
   *dev_out = d;
@@ -254,16 +297,6 @@ static inline size_t xi_dev_values(const mcgpu_ctx* ctx) {
 }
 static inline size_t xi_dev_bytes(const mcgpu_ctx* ctx) { return xi_dev_values(ctx) * (size_t)ctx->xI_bytes; }
 
-// a device array that lives as long as the scope
-template <typename Tp>
-struct DevBuf {
-  Tp* p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc((void**)&p, (n ? n : 1) * sizeof(Tp)); }
-  hipError_t put(const Tp* h, size_t n) { return hipMemcpy(p, h, n * sizeof(Tp), hipMemcpyHostToDevice); }
-  hipError_t get(Tp* h, size_t n) { return hipMemcpy(h, p, n * sizeof(Tp), hipMemcpyDeviceToHost); }
-};
-
 static int fail(mcgpu_ctx* ctx, int code, const char* msg) {
   if (ctx) ctx->err = msg;
   return code;
@@ -279,15 +312,14 @@ extern "C" int mcgpu_create(int device, mcgpu_ctx** out) {
   ctx->device = device;
   std::memset(&ctx->M, 0, sizeof(DevModel));
   if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&ctx->prop, device) != hipSuccess ||
-      hipStreamCreate(&ctx->own_stream) != hipSuccess || hipEventCreate(&ctx->ev0) != hipSuccess ||
-      hipEventCreate(&ctx->ev1) != hipSuccess || hipEventCreate(&ctx->ev_tail) != hipSuccess) {
+      hipStreamCreate(&ctx->own_stream.h) != hipSuccess || hipEventCreate(&ctx->ev0.h) != hipSuccess ||
+      hipEventCreate(&ctx->ev1.h) != hipSuccess || hipEventCreate(&ctx->ev_tail.h) != hipSuccess) {
     delete ctx;
     return MCGPU_ERR_HIP;
   }
   ctx->stream = ctx->own_stream;
   ctx->M.midplane_snap = 0;  // the reference's literal arithmetic; mcgpu_set_midplane_snap(ctx, 1) is the option
-  if (hipMalloc((void**)&ctx->d_counters, CNT_SLOTS * sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc((void**)&ctx->d_err, sizeof(int)) != hipSuccess) {
+  if (ctx->d_counters.resize(CNT_SLOTS) != hipSuccess || ctx->d_err.resize(1) != hipSuccess) {
     delete ctx;
     return MCGPU_ERR_HIP;
   }
@@ -301,39 +333,6 @@ extern "C" int mcgpu_destroy(mcgpu_ctx* ctx) {
   if (!ctx) return MCGPU_OK;
   hipSetDevice(ctx->device);
   hipDeviceSynchronize();
-  for (void* p : ctx->allocs) hipFree(p);
-  if (ctx->d_accum) hipFree(ctx->d_accum);
-  if (ctx->d_counters) hipFree(ctx->d_counters);
-  if (ctx->d_xN) hipFree(ctx->d_xN);
-  if (ctx->d_xJ) hipFree(ctx->d_xJ);
-  nlte_release(ctx, true);
-  if (ctx->d_err) hipFree(ctx->d_err);
-  if (ctx->d_E_prior) hipFree(ctx->d_E_prior);
-  if (ctx->d_xI) hipFree(ctx->d_xI);
-  if (ctx->d_I_spec) hipFree(ctx->d_I_spec);
-  if (ctx->d_vkk) hipFree(ctx->d_vkk);
-  if (ctx->d_I_spec_star) hipFree(ctx->d_I_spec_star);
-  if (ctx->d_prob_E) hipFree(ctx->d_prob_E);
-  if (ctx->d_mono_u64) hipFree(ctx->d_mono_u64);
-  if (ctx->d_mono_i32) hipFree(ctx->d_mono_i32);
-  if (ctx->d_hits) hipFree(ctx->d_hits);
-  if (ctx->d_pool) hipFree(ctx->d_pool);
-  if (ctx->d_pool_blob) hipFree(ctx->d_pool_blob);
-  for (int i = 0; i < 2; ++i) { if (ctx->d_xlog_keys[i]) hipFree(ctx->d_xlog_keys[i]); if (ctx->d_xlog_vals[i]) hipFree(ctx->d_xlog_vals[i]); }
-  if (ctx->d_xlog_rows) hipFree(ctx->d_xlog_rows);
-  if (ctx->d_xlog_ctl) hipFree(ctx->d_xlog_ctl);
-  if (ctx->d_xlog_temp) hipFree(ctx->d_xlog_temp);
-  if (ctx->d_tail_ctl) hipFree(ctx->d_tail_ctl);
-  if (ctx->d_tail_out) hipFree(ctx->d_tail_out);
-  if (ctx->h_arena) hipHostFree(ctx->h_arena);
-  if (ctx->side_stream) hipStreamDestroy(ctx->side_stream);
-  if (ctx->ev_side_in) hipEventDestroy(ctx->ev_side_in);
-  if (ctx->ev_side_out) hipEventDestroy(ctx->ev_side_out);
-  bin_release(ctx);
-  if (ctx->ev0) hipEventDestroy(ctx->ev0);
-  if (ctx->ev1) hipEventDestroy(ctx->ev1);
-  if (ctx->ev_tail) hipEventDestroy(ctx->ev_tail);
-  if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
   delete ctx;
   return MCGPU_OK;
 }
@@ -346,25 +345,14 @@ extern "C" int mcgpu_set_stream(mcgpu_ctx* ctx, void* s) {
   return MCGPU_OK;
 }
 
-extern "C" int mcgpu_set_grid_cyl(mcgpu_ctx* ctx, int n_rad, int nz, int n_az, int l3D,
-                                  const double* r_lim_2, const double* zmax, const double* z_lim,
-                                  const double* tan_phi_lim, double zmaxmax, double Rmax2,
-                                  const double* volume, const int* cell_map, const int* cell_map_i,
-                                  const int* cell_map_j, const int* cell_map_k, const int* lexit_cell) {
-  if (!ctx || n_rad < 1 || nz < 1 || n_az < 1 || !r_lim_2 || !zmax || !z_lim || !tan_phi_lim || !volume ||
-      !cell_map || !cell_map_i || !cell_map_j || !cell_map_k || !lexit_cell)
-    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_grid_cyl: bad argument");
-  if (!l3D && n_az != 1) return fail(ctx, MCGPU_ERR_ARG, "2D grid needs n_az = 1");
-  if (ctx->voro) return fail(ctx, MCGPU_ERR_STATE, "the context already holds a Voronoi grid");
-  HIPCHK(hipSetDevice(ctx->device));
+// The structured grids' cell mapping (both grid types share build_cylindrical_cell_mapping): the kernels evaluate it in
+// closed form, so the host's arrays must be that form
+static int check_cell_map(mcgpu_ctx* ctx, int n_rad, int nz, int n_az, int l3D, const int* cell_map, const int* cell_map_i,
+                          const int* cell_map_j, const int* cell_map_k, const int* lexit_cell) {
   const int n_cells = l3D ? 2 * n_rad * nz * n_az : n_rad * nz;
   const int jlo = l3D ? -nz - 1 : 0;
-  ctx->h_r_lim.resize((size_t)n_rad + 1);
-  for (int i = 0; i <= n_rad; ++i) ctx->h_r_lim[i] = std::sqrt(r_lim_2[i]);
-  ctx->tau_midplane = -1.0; ctx->last_inter_pp = -1.0;
   const int jn = nz + 1 - jlo + 1;
   const int ntot2 = l3D ? (n_rad + 2) * (2 * nz + 2) * n_az : (n_rad + 2) * (nz + 2) * n_az;
-  // verify the closed-form mapping against the host's arrays
   for (int k = 1; k <= n_az; ++k)
     for (int j = jlo; j <= nz + 1; ++j) {
       if (l3D && j == 0) continue;
@@ -383,6 +371,27 @@ extern "C" int mcgpu_set_grid_cyl(mcgpu_ctx* ctx, int n_rad, int nz, int n_az, i
         if (lexit_cell[ic - 1] != le) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "lexit_cell differs from the reference rule");
       }
     }
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_set_grid_cyl(mcgpu_ctx* ctx, int n_rad, int nz, int n_az, int l3D,
+                                  const double* r_lim_2, const double* zmax, const double* z_lim,
+                                  const double* tan_phi_lim, double zmaxmax, double Rmax2,
+                                  const double* volume, const int* cell_map, const int* cell_map_i,
+                                  const int* cell_map_j, const int* cell_map_k, const int* lexit_cell) {
+  if (!ctx || n_rad < 1 || nz < 1 || n_az < 1 || !r_lim_2 || !zmax || !z_lim || !tan_phi_lim || !volume ||
+      !cell_map || !cell_map_i || !cell_map_j || !cell_map_k || !lexit_cell)
+    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_grid_cyl: bad argument");
+  if (!l3D && n_az != 1) return fail(ctx, MCGPU_ERR_ARG, "2D grid needs n_az = 1");
+  if (ctx->voro) return fail(ctx, MCGPU_ERR_STATE, "the context already holds a Voronoi grid");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int n_cells = l3D ? 2 * n_rad * nz * n_az : n_rad * nz;
+  ctx->h_r_lim.resize((size_t)n_rad + 1);
+  for (int i = 0; i <= n_rad; ++i) ctx->h_r_lim[i] = std::sqrt(r_lim_2[i]);
+  ctx->tau_midplane = -1.0; ctx->last_inter_pp = -1.0;
+  const int ntot2 = l3D ? (n_rad + 2) * (2 * nz + 2) * n_az : (n_rad + 2) * (nz + 2) * n_az;
+  int rc = check_cell_map(ctx, n_rad, nz, n_az, l3D, cell_map, cell_map_i, cell_map_j, cell_map_k, lexit_cell);
+  if (rc) return rc;
   // verify the uniform vertical grid the kernel evaluates in closed form
   std::vector<double> ch(n_rad);
   for (int i = 1; i <= n_rad; ++i) {
@@ -397,7 +406,6 @@ extern "C" int mcgpu_set_grid_cyl(mcgpu_ctx* ctx, int n_rad, int nz, int n_az, i
   DevModel& M = ctx->M;
   M.n_rad = n_rad; M.nz = nz; M.n_az = n_az; M.l3D = l3D ? 1 : 0; M.n_cells = n_cells;
   M.zmaxmax = zmaxmax; M.Rmax2 = Rmax2;
-  int rc;
   if ((rc = upload(ctx, r_lim_2, (size_t)n_rad + 1, &M.r_lim_2))) return rc;
   if ((rc = upload(ctx, zmax, (size_t)n_rad, &M.zmax))) return rc;
   if ((rc = upload(ctx, ch.data(), (size_t)n_rad, &M.ch))) return rc;
@@ -428,31 +436,15 @@ extern "C" int mcgpu_set_grid_sph(mcgpu_ctx* ctx, int n_rad, int nz, int n_az, i
   if (ctx->have_grid) return fail(ctx, MCGPU_ERR_STATE, "the grid of a context is set once");
   HIPCHK(hipSetDevice(ctx->device));
   const int n_cells = l3D ? 2 * n_rad * nz * n_az : n_rad * nz;
-  const int jlo = l3D ? -nz - 1 : 0;
-  const int jn = nz + 1 - jlo + 1;
   const int ntot2 = l3D ? (n_rad + 2) * (2 * nz + 2) * n_az : (n_rad + 2) * (nz + 2) * n_az;
-  for (int k = 1; k <= n_az; ++k)   // the closed-form mapping of build_cylindrical_cell_mapping, as for the cylindrical grid
-    for (int j = jlo; j <= nz + 1; ++j) {
-      if (l3D && j == 0) continue;
-      for (int i = 0; i <= n_rad + 1; ++i) {
-        const int ic = cell_map[i + (n_rad + 2) * ((j - jlo) + jn * (k - 1))];
-        if (ic != icell_of(n_rad, nz, n_az, l3D, i, j, k))
-          return fail(ctx, MCGPU_ERR_UNSUPPORTED, "cell_map differs from build_cylindrical_cell_mapping order");
-        if (ic < 1 || ic > ntot2 || cell_map_i[ic - 1] != i || cell_map_j[ic - 1] != j || cell_map_k[ic - 1] != k)
-          return fail(ctx, MCGPU_ERR_UNSUPPORTED, "cell_map_i/j/k inconsistent with cell_map");
-        int le = 0;
-        const int aj = j < 0 ? -j : j;
-        if (ic > n_cells) { if (i == n_rad + 1) le = 1; else if (aj == nz + 1) le = 2; }
-        if (lexit_cell[ic - 1] != le) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "lexit_cell differs from the reference rule");
-      }
-    }
+  int rc = check_cell_map(ctx, n_rad, nz, n_az, l3D, cell_map, cell_map_i, cell_map_j, cell_map_k, lexit_cell);
+  if (rc) return rc;
   for (int j = 1; j <= nz; ++j)
     if (!(tan_theta_lim[j] > tan_theta_lim[j - 1])) return fail(ctx, MCGPU_ERR_ARG, "tan_theta_lim must increase");
   DevModel& M = ctx->M;
   M.n_rad = n_rad; M.nz = nz; M.n_az = n_az; M.l3D = l3D ? 1 : 0; M.n_cells = n_cells;
   M.zmaxmax = 0.0; M.Rmax2 = Rmax2; M.grid_sph = 1;
   std::vector<double> ones(n_rad, 1.0);   // (the cylindrical vectors the shared LDS carve stages; unused by this grid)
-  int rc;
   if ((rc = upload(ctx, r_lim_2, (size_t)n_rad + 1, &M.r_lim_2))) return rc;
   if ((rc = upload(ctx, ones.data(), (size_t)n_rad, &M.zmax))) return rc;
   if ((rc = upload(ctx, ones.data(), (size_t)n_rad, &M.ch))) return rc;
@@ -558,33 +550,21 @@ extern "C" int mcgpu_set_grid_voronoi(mcgpu_ctx* ctx, int n_cells, const float* 
 // the option that sizes it changes)
 // what was sized for the grid that is being replaced
 static void grid_release(mcgpu_ctx* ctx) {
-  if (ctx->d_prob_E) hipFree(ctx->d_prob_E);
-  ctx->d_prob_E = nullptr;
+  ctx->d_prob_E.reset();
   ctx->prob_E_lambda = 0;
-  if (ctx->d_xN) hipFree(ctx->d_xN);
-  ctx->d_xN = nullptr;
-  if (ctx->d_xJ) hipFree(ctx->d_xJ);
-  ctx->d_xJ = nullptr;
+  ctx->d_xN.reset();
+  ctx->d_xJ.reset();
+  ctx->d_E_prior.reset();
   nlte_release(ctx, true);   // (the non-LTE tables, J0 and xJ_abs are per cell)
 }
 
 static void bin_release(mcgpu_ctx* ctx) {
-  if (ctx->bin.keys) hipFree(ctx->bin.keys);
-  if (ctx->bin.vals) hipFree(ctx->bin.vals);
-  if (ctx->bin.count) hipFree(ctx->bin.count);
-  if (ctx->bin.stats) hipFree(ctx->bin.stats);
-  if (ctx->d_bin_off) hipFree(ctx->d_bin_off);
-  if (ctx->d_bin_cap) hipFree(ctx->d_bin_cap);
-  if (ctx->d_bin_want) hipFree(ctx->d_bin_want);
-  ctx->d_bin_want = nullptr;
-  for (int i = 0; i < 2; ++i) { if (ctx->d_carry[i]) hipFree(ctx->d_carry[i]); ctx->d_carry[i] = nullptr; }
-  if (ctx->d_carry_n) hipFree(ctx->d_carry_n);
-  if (ctx->d_tail_next) hipFree(ctx->d_tail_next);
-  ctx->d_carry_n = nullptr;
-  ctx->d_tail_next = nullptr;
-  ctx->carry_cap = 0;
+  ctx->d_bin_keys.reset(); ctx->d_bin_vals.reset(); ctx->d_bin_count.reset(); ctx->d_bin_stats.reset();
+  ctx->d_bin_off.reset(); ctx->d_bin_cap.reset(); ctx->d_bin_want.reset();
+  for (int i = 0; i < 2; ++i) ctx->d_carry[i].reset();
+  ctx->d_carry_n.reset();
+  ctx->d_tail_next.reset();
   ctx->bin = BinLog{};
-  ctx->d_bin_off = ctx->d_bin_cap = nullptr;
   ctx->bin_total_blocks = 0;
   ctx->bin_max_parts = 0;
 }
@@ -1013,9 +993,10 @@ extern "C" int mcgpu_build_ksca_CDF(mcgpu_ctx* ctx, int build, double* ksca_CDF_
   HIPCHK(hipSetDevice(ctx->device));
   const int ng = M.m1_ng, nc = M.n_classes, nl = M.n_lambda;
   const size_t n = (size_t)nc * nl * (ng + 1);
-  double* d = nullptr;
-  HIPCHK(hipMalloc((void**)&d, n * sizeof(double)));
-  ctx->allocs.push_back(d);
+  DevArr<char> a;
+  HIPCHK(a.resize(n * sizeof(double)));
+  double* d = reinterpret_cast<double*>(a.p);
+  ctx->allocs.push_back(std::move(a));
   hipLaunchKernelGGL(k_ksca_cdf, dim3((unsigned)((nc * nl + 127) / 128)), dim3(128), 0, ctx->stream, nc, nl, ng, M.m1_Csca, M.m1_dens,
                      M.m1_nk, d);
   HIPCHK(hipGetLastError());
@@ -1050,12 +1031,12 @@ extern "C" int mcgpu_opacity(mcgpu_ctx* ctx, const mcgpu_grain_tables* G, int p_
   HIPCHK(hipSetDevice(ctx->device));
   int rc;
   // the grains' tables: here for the time of the call
-  DevBuf<float> dCe, dCs, dCa, dg, d11, d12, d22, d33, d34, d44, dS;
-  DevBuf<double> dn, dd;
+  DevArr<float> dCe, dCs, dCa, dg, d11, d12, d22, d33, d34, d44, dS;
+  DevArr<double> dn, dd;
   auto put = [&](auto& buf, const auto* host, size_t n) -> int {
     if (!host) return MCGPU_OK;
     using Tp = std::remove_cv_t<std::remove_pointer_t<decltype(host)>>;
-    HIPCHK(hipMalloc((void**)&buf.p, n * sizeof(Tp)));
+    HIPCHK(buf.resize(n));
     HIPCHK(hipMemcpyAsync(buf.p, host, n * sizeof(Tp), hipMemcpyHostToDevice, ctx->stream));
     return MCGPU_OK;
   };
@@ -1071,11 +1052,6 @@ extern "C" int mcgpu_opacity(mcgpu_ctx* ctx, const mcgpu_grain_tables* G, int p_
       return rc;
   }
   // the context's per-class tables (mcgpu_set_variable_dust's): built in place; those of the last call go
-  for (void* q : ctx->opacity_allocs) {
-    for (auto it = ctx->allocs.begin(); it != ctx->allocs.end(); ++it)
-      if (*it == q) { ctx->allocs.erase(it); break; }
-    hipFree(q);
-  }
   ctx->opacity_allocs.clear();
   M.n_classes = 0;
   M.m1 = 0;
@@ -1093,7 +1069,8 @@ extern "C" int mcgpu_opacity(mcgpu_ctx* ctx, const mcgpu_grain_tables* G, int p_
       (rc = upload<float>(ctx, nullptr, 0, &M.v_s33, n_cla)) || (rc = upload<float>(ctx, nullptr, 0, &M.v_s34, n_cla)) ||
       (rc = upload<float>(ctx, nullptr, 0, &M.v_s44, n_cla)))
     return rc;
-  ctx->opacity_allocs.assign(ctx->allocs.begin() + allocs_before, ctx->allocs.end());
+  for (size_t i = allocs_before; i < ctx->allocs.size(); ++i) ctx->opacity_allocs.push_back(std::move(ctx->allocs[i]));
+  ctx->allocs.resize(allocs_before);
   OpacityIn I{ng, nl, nc, M.nang, M.aniso_method, pola ? 1 : 0, G->grain_RE_LTE_start, G->grain_RE_LTE_end, pcols,
               dCe.p, dCs.p, dCa.p, dg.p, d11.p, d12.p, d22.p, d33.p, d34.p, d44.p, dS.p, dn.p, dd.p};
   OpacityOut O{const_cast<double*>(M.v_kappa), const_cast<double*>(M.v_kabs), const_cast<float*>(M.v_albedo), const_cast<float*>(M.v_g),
@@ -1164,48 +1141,43 @@ extern "C" int mcgpu_init_reemission_ex(mcgpu_ctx* ctx, const double* tab_lambda
   for (int l = 0; l < nl; ++l)
     if (!(tab_lambda[l] > 0.0) || !(tab_delta_lambda[l] > 0.0))
       return fail(ctx, MCGPU_ERR_ARG, "mcgpu_init_reemission: wavelengths and bin widths must be positive");
-  double *d_lam = nullptr, *d_dlam = nullptr;
-  HIPCHK(hipMalloc((void**)&d_lam, 2 * (size_t)nl * sizeof(double)));
-  d_dlam = d_lam + nl;
-  hipError_t e = hipMemcpy(d_lam, tab_lambda, (size_t)nl * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_dlam, tab_delta_lambda, (size_t)nl * sizeof(double), hipMemcpyHostToDevice);
+  DevArr<double> d_lam, d_dudt;
+  HIPCHK(d_lam.resize(2 * (size_t)nl));
+  double* const d_dlam = d_lam + nl;
+  HIPCHK(hipMemcpy(d_lam, tab_lambda, (size_t)nl * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_dlam, tab_delta_lambda, (size_t)nl * sizeof(double), hipMemcpyHostToDevice));
   // the extra heating's per-class terms (they belong to the tables the loop reads: the classes' when there are classes)
   const int n_heat = M.n_classes ? M.n_classes : 1;
-  double *d_dudt = nullptr, *d_hnorm = nullptr;
-  if (dudt && e == hipSuccess) {
+  double* d_hnorm = nullptr;
+  if (dudt) {
     for (int c = 0; c < n_heat; ++c)
-      if (!(heating_norm[c] > 0.0)) { hipFree(d_lam); return fail(ctx, MCGPU_ERR_ARG, "mcgpu_init_reemission: heating_norm must be positive"); }
-    e = hipMalloc((void**)&d_dudt, 2 * (size_t)n_heat * sizeof(double));
-    if (e == hipSuccess) { d_hnorm = d_dudt + n_heat; e = hipMemcpy(d_dudt, dudt, (size_t)n_heat * sizeof(double), hipMemcpyHostToDevice); }
-    if (e == hipSuccess) e = hipMemcpy(d_hnorm, heating_norm, (size_t)n_heat * sizeof(double), hipMemcpyHostToDevice);
+      if (!(heating_norm[c] > 0.0)) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_init_reemission: heating_norm must be positive");
+    HIPCHK(d_dudt.resize(2 * (size_t)n_heat));
+    d_hnorm = d_dudt + n_heat;
+    HIPCHK(hipMemcpy(d_dudt, dudt, (size_t)n_heat * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_hnorm, heating_norm, (size_t)n_heat * sizeof(double), hipMemcpyHostToDevice));
   }
   auto build = [&](int nc, const double* kabs, const double* lq, const double* cdf, bool heat) {
     const int n = nc * nT, threads = 64;  // one (class, T) row per thread: short rows, many of them
     hipLaunchKernelGGL(k_init_reemission, dim3((n + threads - 1) / threads), dim3(threads), 0, ctx->stream, nc, nT, nl,
                        ctx->d_tab_Temp, d_lam, d_dlam, kabs, const_cast<double*>(lq), const_cast<double*>(cdf),
-                       heat ? d_dudt : nullptr, heat ? d_hnorm : nullptr, ufac_implicit);
+                       heat ? d_dudt.p : nullptr, heat ? d_hnorm : nullptr, ufac_implicit);
   };
   // the tables the setters left to this call; called with none pending, it rebuilds all of them (an explicit request),
   // otherwise tables the host supplied are left alone
   const bool all = !ctx->pending_single && !ctx->pending_classes;
   const bool do_single = all || ctx->pending_single, do_classes = M.n_classes && (all || ctx->pending_classes);
-  if (e == hipSuccess) {
-    if (do_single) build(1, M.kappa_abs, M.log_Qcool, M.cdf, !M.n_classes);
-    if (do_classes) build(M.n_classes, M.v_kabs, M.v_lq, M.v_cdf, true);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (do_single) build(1, M.kappa_abs, M.log_Qcool, M.cdf, !M.n_classes);
+  if (do_classes) build(M.n_classes, M.v_kabs, M.v_lq, M.v_cdf, true);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   // the same gate as the setters: Temp_LTE's search needs log_Qcool to increase with T
   const int nc = M.n_classes ? M.n_classes : 1;
   const double* d_lq = M.n_classes ? M.v_lq : M.log_Qcool;
   const double* d_cdf = M.n_classes ? M.v_cdf : M.cdf;
   std::vector<double> lq((size_t)nc * nT);
-  if (e == hipSuccess) e = hipMemcpy(lq.data(), d_lq, lq.size() * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && kdB_dT_CDF)
-    e = hipMemcpy(kdB_dT_CDF, d_cdf, (size_t)nc * nT * nl * sizeof(double), hipMemcpyDeviceToHost);
-  hipFree(d_lam);
-  if (d_dudt) hipFree(d_dudt);
-  if (e != hipSuccess) return fail(ctx, MCGPU_ERR_HIP, hipGetErrorString(e));
+  HIPCHK(hipMemcpy(lq.data(), d_lq, lq.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (kdB_dT_CDF) HIPCHK(hipMemcpy(kdB_dT_CDF, d_cdf, (size_t)nc * nT * nl * sizeof(double), hipMemcpyDeviceToHost));
   if (log_Qcool) std::memcpy(log_Qcool, lq.data(), lq.size() * sizeof(double));
   // (a table that fails the gate stays in the context -- it was built in place --, so the context is marked as waiting for
   // its re-emission tables again: ready() refuses every launch until a build, or tables from the host, pass)
@@ -1322,12 +1294,9 @@ static size_t n_sed(const DevModel& M) { return (size_t)MCGPU_N_SED_TYPES * M.n_
 static int ensure_accum(mcgpu_ctx* ctx) {
   const DevModel& M = ctx->M;
   const size_t n = (size_t)M.n_cells + n_sed(M) + M.n_lambda + MCGPU_N_COUNTERS;
-  if (ctx->d_accum && ctx->n_accum == n) return MCGPU_OK;
-  if (ctx->d_accum) hipFree(ctx->d_accum);
-  ctx->d_accum = nullptr;
-  HIPCHK(hipMalloc((void**)&ctx->d_accum, n * sizeof(double)));
+  if (ctx->d_accum && ctx->d_accum.n == n) return MCGPU_OK;
+  HIPCHK(ctx->d_accum.resize(n));
   HIPCHK(hipMemset(ctx->d_accum, 0, n * sizeof(double)));
-  ctx->n_accum = n;
   return MCGPU_OK;
 }
 
@@ -1344,7 +1313,7 @@ static int ready(mcgpu_ctx* ctx) {
 extern "C" int mcgpu_set_E_prior(mcgpu_ctx* ctx, const double* E_prior) {
   if (!ctx || !E_prior || !ctx->have_grid) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_E_prior: bad argument");
   HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->d_E_prior) HIPCHK(hipMalloc((void**)&ctx->d_E_prior, (size_t)ctx->M.n_cells * sizeof(double)));
+  HIPCHK(ctx->d_E_prior.resize((size_t)ctx->M.n_cells));
   HIPCHK(hipMemcpy(ctx->d_E_prior, E_prior, (size_t)ctx->M.n_cells * sizeof(double), hipMemcpyHostToDevice));
   return MCGPU_OK;
 }
@@ -1364,15 +1333,16 @@ static int tail_threshold(const mcgpu_ctx* ctx) {
 
 // the record buffers a role kernel hands unfinished packets over in (chunks of a binned run: two, used in turns; the
 // tail kernel: one): per workgroup its records, a packet per lane and a batch of work items per wave
+static inline size_t carry_cap(const mcgpu_ctx* ctx) { return ctx->d_carry[1] ? ctx->d_carry[1].n / sizeof(Rec<true>) : 0; }   // records per buffer
+
 static int carry_prepare(mcgpu_ctx* ctx, int n_wg, int n_rec, int threads) {
   const size_t cap = (size_t)n_wg * ((size_t)n_rec + threads + (size_t)(threads / 64) * PK_BATCH);
-  if (ctx->carry_cap < cap || !ctx->d_carry[0]) {
-    for (int i = 0; i < 2; ++i) { if (ctx->d_carry[i]) hipFree(ctx->d_carry[i]); ctx->d_carry[i] = nullptr; }
-    for (int i = 0; i < 2; ++i) HIPCHK(hipMalloc(&ctx->d_carry[i], cap * sizeof(Rec<true>)));
-    ctx->carry_cap = cap;
+  if (carry_cap(ctx) < cap) {
+    for (int i = 0; i < 2; ++i) ctx->d_carry[i].reset();
+    for (int i = 0; i < 2; ++i) HIPCHK(ctx->d_carry[i].resize(cap * sizeof(Rec<true>)));
   }
-  if (!ctx->d_carry_n) HIPCHK(hipMalloc((void**)&ctx->d_carry_n, 2 * sizeof(unsigned int)));
-  if (!ctx->d_tail_next) HIPCHK(hipMalloc((void**)&ctx->d_tail_next, sizeof(unsigned int)));
+  HIPCHK(ctx->d_carry_n.reserve(2));
+  HIPCHK(ctx->d_tail_next.reserve(1));
   return MCGPU_OK;
 }
 
@@ -1392,7 +1362,8 @@ static void host_tail_callback(void* p) {   // (runs on a thread of the HIP runt
   HostTailCall* c = static_cast<HostTailCall*>(p);
   mcgpu_ctx* ctx = c->ctx;
   unsigned int n = c->h_ctl[1];
-  if (n > ctx->tail_out_cap) n = ctx->tail_out_cap;   // (k_tail reported error 17)
+  const unsigned int cap = (unsigned int)(ctx->d_tail_out.n / sizeof(Rec<true>));
+  if (n > cap) n = cap;   // (k_tail reported error 17)
   c->job.n = (*c->h_err == 0) ? n : 0u;
   mcgpu_host::run_tail(&c->job);
   ctx->host_tail_ms = c->job.ms; ctx->host_tail_packets = c->job.n; ctx->host_tail_threads = c->job.threads_used;
@@ -1438,25 +1409,22 @@ static int launch_tail(mcgpu_ctx* ctx, const RunArgs& A_in, const void* carry, c
     n_threads = ctx->opt_host_threads > 0 ? ctx->opt_host_threads : mcgpu_host::default_threads(n_dev);
     mcgpu_host::prepare_threads(n_threads);
     host_max = ctx->opt_tail_host_max > 0 ? (unsigned int)ctx->opt_tail_host_max : 8u * (unsigned int)n_threads;
-    if (!ctx->d_tail_ctl) HIPCHK(hipMalloc((void**)&ctx->d_tail_ctl, 2 * sizeof(unsigned int)));
-    if (ctx->tail_out_cap < host_max) {
+    HIPCHK(ctx->d_tail_ctl.reserve(2));
+    if (ctx->d_tail_out.n < (size_t)host_max * sizeof(Rec<true>)) {
       HIPCHK(hipStreamSynchronize(ctx->stream));   // (an earlier launch may still write the old buffer)
-      if (ctx->d_tail_out) hipFree(ctx->d_tail_out);
-      ctx->d_tail_out = nullptr; ctx->tail_out_cap = 0;
-      HIPCHK(hipMalloc(&ctx->d_tail_out, (size_t)host_max * sizeof(Rec<true>)));
-      ctx->tail_out_cap = host_max;
+      HIPCHK(ctx->d_tail_out.resize((size_t)host_max * sizeof(Rec<true>)));
     }
     if (!ctx->side_stream) {
-      HIPCHK(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&ctx->ev_side_in, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&ctx->ev_side_out, hipEventDisableTiming));
+      HIPCHK(hipStreamCreateWithFlags(&ctx->side_stream.h, hipStreamNonBlocking));
+      HIPCHK(hipEventCreateWithFlags(&ctx->ev_side_in.h, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&ctx->ev_side_out.h, hipEventDisableTiming));
     }
     HIPCHK(hipMemsetAsync(ctx->d_tail_ctl, 0, 2 * sizeof(unsigned int), ctx->stream));
     A.tail_host_max = host_max; A.tail_done = ctx->d_tail_ctl; A.tail_out = ctx->d_tail_out; A.tail_out_n = ctx->d_tail_ctl + 1;
   }
   HIPCHK(hipEventRecord(ctx->ev_tail, ctx->stream));   // (what follows is the launch's tail: mcgpu_get_info "tail_ms")
   ctx->tail_launched = true;
-  void* args[] = {(void*)&M, (void*)&A, (void*)&carry, (void*)&carry_n, (void*)&ctx->d_tail_next};
+  void* args[] = {(void*)&M, (void*)&A, (void*)&carry, (void*)&carry_n, (void*)&ctx->d_tail_next.p};
   HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(MCGPU_TAIL_BLOCK), args, lds, ctx->stream));
   if (!host) return MCGPU_OK;
 
@@ -1503,7 +1471,7 @@ static int launch_tail(mcgpu_ctx* ctx, const RunArgs& A_in, const void* carry, c
   RunArgs& Ha = call->Ah;
   if (Ha.frozen) table((const void**)&Ha.E_prior, (size_t)H.n_cells * sizeof(double)); else Ha.E_prior = nullptr;
   const size_t n_side = segs.size();   // (tables and the prior: constant during the launch -> the side stream)
-  const size_t off_accum = total; total += arena_align(ctx->n_accum * sizeof(double));
+  const size_t off_accum = total; total += arena_align(ctx->d_accum.n * sizeof(double));
   const size_t off_cnt = total; total += arena_align(CNT_SLOTS * sizeof(unsigned long long));
   const size_t off_err = total; total += arena_align(sizeof(int));
   const size_t off_ctl = total; total += arena_align(2 * sizeof(unsigned int));
@@ -1513,8 +1481,8 @@ static int launch_tail(mcgpu_ctx* ctx, const RunArgs& A_in, const void* carry, c
   if (ctx->h_arena_bytes < total) {
     hipError_t e = hipStreamSynchronize(ctx->stream);   // (an earlier launch's callback may still read the old arena)
     if (e == hipSuccess && ctx->h_arena) e = hipHostFree(ctx->h_arena);
-    ctx->h_arena = nullptr; ctx->h_arena_bytes = 0;
-    if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_arena, total + (total >> 2), hipHostMallocDefault);
+    ctx->h_arena.h = nullptr; ctx->h_arena_bytes = 0;
+    if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_arena.h, total + (total >> 2), hipHostMallocDefault);
     if (e != hipSuccess) { delete call; ctx->err = std::string("host tail: pinned arena: ") + hipGetErrorString(e); return MCGPU_ERR_HIP; }
     ctx->h_arena_bytes = total + (total >> 2);
   }
@@ -1545,13 +1513,13 @@ static int launch_tail(mcgpu_ctx* ctx, const RunArgs& A_in, const void* carry, c
   // behind k_tail: what it left, and the sums the host adds to
   HT_CHK(hipMemcpyAsync(base + off_ctl, ctx->d_tail_ctl, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
   HT_CHK(hipMemcpyAsync(base + off_rec, ctx->d_tail_out, (size_t)host_max * rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HT_CHK(hipMemcpyAsync(base + off_accum, ctx->d_accum, ctx->n_accum * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HT_CHK(hipMemcpyAsync(base + off_accum, ctx->d_accum, ctx->d_accum.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HT_CHK(hipMemcpyAsync(base + off_cnt, ctx->d_counters, CNT_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   HT_CHK(hipMemcpyAsync(base + off_err, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HT_CHK(hipStreamWaitEvent(ctx->stream, ctx->ev_side_out, 0));
   HT_CHK(hipLaunchHostFunc(ctx->stream, host_tail_callback, call));
   // (from here on the callback owns `call`)
-  HIPCHK(hipMemcpyAsync(ctx->d_accum, base + off_accum, ctx->n_accum * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->d_accum, base + off_accum, ctx->d_accum.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(ctx->d_counters, base + off_cnt, CNT_SLOTS * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(ctx->d_err, base + off_err, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
 #undef HT_CHK
@@ -1611,9 +1579,8 @@ static int launch_mega(mcgpu_ctx* ctx, const RunArgs& A, bool use_lds, int grid_
       if (ctx->opt_schedule != 1 && !A.xN_abs && !A.xJ_abs && n_rec > 0 && !M.mrw) {  // (the walk: single-role kernel)
         if (!ctx->vkk_valid) {  // (kappa kappa_factor, kappa_abs_LTE) per (cell, wavelength): what a flight reads per cell
           const size_t n = ((size_t)M.n_cells + 1) * M.n_lambda;
-          if (ctx->d_vkk) hipFree(ctx->d_vkk);
-          ctx->d_vkk = nullptr;
-          HIPCHK(hipMalloc((void**)&ctx->d_vkk, n * sizeof(double2)));
+          ctx->d_vkk.reset();
+          HIPCHK(ctx->d_vkk.resize(n));
           hipLaunchKernelGGL(k_build_vkk, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, M, ctx->d_vkk);
           HIPCHK(hipGetLastError());
           ctx->M.v_kk = ctx->d_vkk;
@@ -1682,7 +1649,7 @@ static int launch_mega(mcgpu_ctx* ctx, const RunArgs& A, bool use_lds, int grid_
         int rc = carry_prepare(ctx, rblocks, n_rec, rthreads);
         if (rc) return rc;
         HIPCHK(hipMemsetAsync(ctx->d_carry_n, 0, 2 * sizeof(unsigned int), ctx->stream));
-        At.carry_out = ctx->d_carry[0]; At.carry_out_n = ctx->d_carry_n; At.carry_cap = (unsigned int)ctx->carry_cap;
+        At.carry_out = ctx->d_carry[0]; At.carry_out_n = ctx->d_carry_n; At.carry_cap = (unsigned int)carry_cap(ctx);
         At.tail_threshold = tail_thr;
         fn = kpick_roles_tail(pola, dark, use_lds, M.mrw != 0);
       }
@@ -1766,15 +1733,10 @@ static int launch_voro(mcgpu_ctx* ctx, const RunArgs& A, int grid_blocks, int bl
       const unsigned long long need = (A.n_packets + pthreads - 1) / pthreads;
       if (grid_blocks <= 0 && (unsigned long long)pblocks > need) pblocks = (int)(need ? need : 1);
       const size_t want = (size_t)pblocks * ((size_t)sizeof(PRec) << log_rec);
-      if (ctx->pool_bytes < want) {
-        if (ctx->d_pool) hipFree(ctx->d_pool);
-        ctx->d_pool = nullptr; ctx->pool_bytes = 0;
-        HIPCHK(hipMalloc(&ctx->d_pool, want));
-        ctx->pool_bytes = want;
-      }
+      HIPCHK(ctx->d_pool.reserve(want));
       PoolArgs PA;
-      PA.recs = reinterpret_cast<PRec*>(ctx->d_pool); PA.log_rec = log_rec; PA.cache_log_ns = log_ns;
-      if (!ctx->d_pool_blob) HIPCHK(hipMalloc((void**)&ctx->d_pool_blob, sizeof(VpBlob)));
+      PA.recs = reinterpret_cast<PRec*>(ctx->d_pool.p); PA.log_rec = log_rec; PA.cache_log_ns = log_ns;
+      HIPCHK(ctx->d_pool_blob.reserve(1));
       ctx->h_pool_blob.M = M; ctx->h_pool_blob.A = A; ctx->h_pool_blob.G = ctx->V;
       // (pageable host memory: a synchronous copy -- behind the stream's earlier work -- so that a second launch enqueued
       // right after this one cannot overwrite the blob before it has been read)
@@ -1933,13 +1895,14 @@ static int bin_prepare(mcgpu_ctx* ctx, int n_parts, uint64_t n_packets) {
   unsigned long long blocks = bytes / block_bytes;
   if (blocks < least) blocks = least;
   if (blocks > 0xFFFFFFFFull) blocks = 0xFFFFFFFFull;  // (block indices are 32-bit)
-  HIPCHK(hipMalloc((void**)&ctx->bin.keys, blocks * BIN_H * sizeof(unsigned int)));
-  HIPCHK(hipMalloc((void**)&ctx->bin.vals, blocks * BIN_H * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&ctx->bin.count, (size_t)nb * n_parts * sizeof(unsigned int)));
-  HIPCHK(hipMalloc((void**)&ctx->bin.stats, 2 * sizeof(unsigned long long)));
-  HIPCHK(hipMalloc((void**)&ctx->d_bin_off, nb * sizeof(unsigned int)));
-  HIPCHK(hipMalloc((void**)&ctx->d_bin_cap, nb * sizeof(unsigned int)));
-  HIPCHK(hipMalloc((void**)&ctx->d_bin_want, nb * sizeof(double)));
+  HIPCHK(ctx->d_bin_keys.resize(blocks * BIN_H));
+  HIPCHK(ctx->d_bin_vals.resize(blocks * BIN_H));
+  HIPCHK(ctx->d_bin_count.resize((size_t)nb * n_parts));
+  HIPCHK(ctx->d_bin_stats.resize(2));
+  HIPCHK(ctx->d_bin_off.resize(nb));
+  HIPCHK(ctx->d_bin_cap.resize(nb));
+  HIPCHK(ctx->d_bin_want.resize(nb));
+  ctx->bin.keys = ctx->d_bin_keys; ctx->bin.vals = ctx->d_bin_vals; ctx->bin.count = ctx->d_bin_count; ctx->bin.stats = ctx->d_bin_stats;
   HIPCHK(hipMemset(ctx->bin.count, 0, (size_t)nb * n_parts * sizeof(unsigned int)));
   HIPCHK(hipMemset(ctx->bin.stats, 0, 2 * sizeof(unsigned long long)));
   ctx->bin.off = ctx->d_bin_off; ctx->bin.cap = ctx->d_bin_cap;
@@ -2027,7 +1990,7 @@ static int launch_binned(mcgpu_ctx* ctx, RunArgs A, const mcgpu_run_opts* o) {
       const bool to_tail = last && tail_thr > 0;
       A.carry_in = ctx->d_carry[in]; A.carry_in_n = ctx->d_carry_n + in;
       A.carry_out = (last && !to_tail) ? nullptr : ctx->d_carry[out]; A.carry_out_n = ctx->d_carry_n + out;
-      A.carry_cap = (unsigned int)ctx->carry_cap;
+      A.carry_cap = (unsigned int)carry_cap(ctx);
       A.tail_threshold = to_tail ? tail_thr : 0;
       if (!last || to_tail) HIPCHK(hipMemsetAsync(ctx->d_carry_n + out, 0, sizeof(unsigned int), ctx->stream));
     }
@@ -2068,7 +2031,7 @@ extern "C" int mcgpu_launch_thermal(mcgpu_ctx* ctx, const mcgpu_run_opts* o) {
   if (lds > (size_t)ctx->prop.sharedMemPerBlock && lds > 160 * 1024)
     return fail(ctx, MCGPU_ERR_UNSUPPORTED, "wavelength tables exceed the LDS of one CU");
   if (!o->accumulate) {
-    HIPCHK(hipMemsetAsync(ctx->d_accum, 0, ctx->n_accum * sizeof(double), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_accum, 0, ctx->d_accum.n * sizeof(double), ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_counters, 0, CNT_SLOTS * sizeof(unsigned long long), ctx->stream));
   } else {
     HIPCHK(hipMemsetAsync(ctx->d_counters + WORK_SLOT, 0, sizeof(unsigned long long), ctx->stream));
@@ -2095,13 +2058,13 @@ extern "C" int mcgpu_launch_thermal(mcgpu_ctx* ctx, const mcgpu_run_opts* o) {
   A.min_active = tune("MCGPU_MIN_ACTIVE", ctx->voro ? 48 : 32, 0, 64);
   A.flags = tune("MCGPU_DIAG_FLAGS", 0, 0, 0x7FFFFFFF);  // (diagnostic builds only)
   if (ctx->opt_radiation_field & 1) {
-    if (!ctx->d_xN) { HIPCHK(hipMalloc((void**)&ctx->d_xN, (size_t)M.n_cells * sizeof(unsigned long long))); HIPCHK(hipMemset(ctx->d_xN, 0, (size_t)M.n_cells * sizeof(unsigned long long))); }
+    if (!ctx->d_xN) { HIPCHK(ctx->d_xN.resize((size_t)M.n_cells)); HIPCHK(hipMemset(ctx->d_xN, 0, (size_t)M.n_cells * sizeof(unsigned long long))); }
     if (!o->accumulate) HIPCHK(hipMemsetAsync(ctx->d_xN, 0, (size_t)M.n_cells * sizeof(unsigned long long), ctx->stream));
     A.xN_abs = ctx->d_xN;
   }
   if (ctx->opt_radiation_field & 2) {
     const size_t nj = (size_t)M.n_cells * M.n_lambda;
-    if (!ctx->d_xJ) { HIPCHK(hipMalloc((void**)&ctx->d_xJ, nj * sizeof(double))); HIPCHK(hipMemset(ctx->d_xJ, 0, nj * sizeof(double))); }
+    if (!ctx->d_xJ) { HIPCHK(ctx->d_xJ.resize(nj)); HIPCHK(hipMemset(ctx->d_xJ, 0, nj * sizeof(double))); }
     if (!o->accumulate) HIPCHK(hipMemsetAsync(ctx->d_xJ, 0, nj * sizeof(double), ctx->stream));
     A.xJ_abs = ctx->d_xJ;
   }
@@ -2191,7 +2154,7 @@ extern "C" int mcgpu_device_accumulators(mcgpu_ctx* ctx, void** accum_dev, uint6
   HIPCHK(hipSetDevice(ctx->device));
   if ((rc = ensure_accum(ctx))) return rc;
   if (accum_dev) *accum_dev = ctx->d_accum;
-  if (n_doubles) *n_doubles = ctx->n_accum;
+  if (n_doubles) *n_doubles = ctx->d_accum.n;
   if (counters_dev) *counters_dev = ctx->d_counters;
   return MCGPU_OK;
 }
@@ -2254,7 +2217,7 @@ extern "C" int mcgpu_counters_to_accum(mcgpu_ctx* ctx) {
   if (!ctx->d_accum) return fail(ctx, MCGPU_ERR_STATE, "nothing launched yet");
   HIPCHK(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_counters_to_accum, dim3(1), dim3(64), 0, ctx->stream, ctx->d_counters,
-                     ctx->d_accum + (ctx->n_accum - MCGPU_N_COUNTERS));
+                     ctx->d_accum + (ctx->d_accum.n - MCGPU_N_COUNTERS));
   HIPCHK(hipGetLastError());
   return MCGPU_OK;
 }
@@ -2265,7 +2228,7 @@ extern "C" int mcgpu_counters_from_accum(mcgpu_ctx* ctx) {
   if (!ctx->d_accum) return fail(ctx, MCGPU_ERR_STATE, "nothing launched yet");
   HIPCHK(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_counters_from_accum, dim3(1), dim3(64), 0, ctx->stream, ctx->d_counters,
-                     ctx->d_accum + (ctx->n_accum - MCGPU_N_COUNTERS));
+                     ctx->d_accum + (ctx->d_accum.n - MCGPU_N_COUNTERS));
   HIPCHK(hipGetLastError());
   return MCGPU_OK;
 }
@@ -2300,18 +2263,18 @@ extern "C" int mcgpu_repartition_energie(mcgpu_ctx* ctx, int lambda, double wl_u
                                                "reference never builds such weights, thermal_emission.f90:2078-2135; the packet-weight half, "
                                                "dust_transfer.f90:1140-1142, is not built)");
   HIPCHK(hipSetDevice(ctx->device));
-  DevBuf<float> d_T, d_w;
-  DevBuf<double> d_E, d_Ec, d_tot;
-  HIPCHK(hipMalloc((void**)&d_T.p, (size_t)n * sizeof(float)));
-  HIPCHK(hipMalloc((void**)&d_E.p, (size_t)n * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&d_Ec.p, (size_t)n * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&d_tot.p, 2 * sizeof(double)));
+  DevArr<float> d_T, d_w;
+  DevArr<double> d_E, d_Ec, d_tot;
+  HIPCHK(d_T.resize((size_t)n));
+  HIPCHK(d_E.resize((size_t)n));
+  HIPCHK(d_Ec.resize((size_t)n));
+  HIPCHK(d_tot.resize(2));
   HIPCHK(hipMemcpyAsync(d_T.p, Tdust, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   if (weight_proba_emission) {
-    HIPCHK(hipMalloc((void**)&d_w.p, (size_t)n * sizeof(float)));
+    HIPCHK(d_w.resize((size_t)n));
     HIPCHK(hipMemcpyAsync(d_w.p, weight_proba_emission, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   }
-  if (!ctx->d_prob_E) HIPCHK(hipMalloc((void**)&ctx->d_prob_E, ((size_t)n + 1) * sizeof(double)));
+  HIPCHK(ctx->d_prob_E.reserve((size_t)n + 1));
   const double wl = wl_um * (double)1.e-6f;  // (:1804: the default-real literal 1.e-6)
   hipLaunchKernelGGL(k_repart_E_cell, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, M, lambda, wl, d_T.p, d_w.p, d_E.p, d_Ec.p);
   if (ctx->nl.d_T1 && (!ctx->nl.d_Cabs || ctx->nl.T1_grains != ctx->nl.n_grains || ctx->nl.dim_lambda != M.n_lambda || ctx->nl.dim_cells != M.n_cells))
@@ -2455,12 +2418,10 @@ extern "C" int mcgpu_set_rt2(mcgpu_ctx* ctx, int n_theta_I, int n_phi_I, int N_t
     return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_rt2: N_type_flux = n_Stokes (+ 4 with lsepar_contrib)");
   if (ctx->M.l3D || ctx->voro) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "ray tracing method 2 is for 2D grids (cylindrical or spherical)");
   HIPCHK(hipSetDevice(ctx->device));
-  if (ctx->d_I_spec) hipFree(ctx->d_I_spec);
-  if (ctx->d_I_spec_star) hipFree(ctx->d_I_spec_star);
-  ctx->d_I_spec = ctx->d_I_spec_star = nullptr; ctx->have_rt2 = false;
+  ctx->d_I_spec.reset(); ctx->d_I_spec_star.reset(); ctx->have_rt2 = false;
   const size_t n = (size_t)ctx->M.n_cells * n_phi_I * n_theta_I * XI_LINE;
-  HIPCHK(hipMalloc((void**)&ctx->d_I_spec, n * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&ctx->d_I_spec_star, (size_t)ctx->M.n_cells * sizeof(double)));
+  HIPCHK(ctx->d_I_spec.resize(n));
+  HIPCHK(ctx->d_I_spec_star.resize((size_t)ctx->M.n_cells));
   HIPCHK(hipMemset(ctx->d_I_spec, 0, n * sizeof(double)));
   HIPCHK(hipMemset(ctx->d_I_spec_star, 0, (size_t)ctx->M.n_cells * sizeof(double)));
   ctx->n_theta_I = n_theta_I; ctx->n_phi_I = n_phi_I; ctx->rt2_N_type_flux = N_type_flux; ctx->rt2_contrib = lsepar_contrib ? 1 : 0;
@@ -2501,8 +2462,8 @@ extern "C" int mcgpu_set_I_spec(mcgpu_ctx* ctx, const double* I_spec, const doub
   HIPCHK(hipSetDevice(ctx->device));
   const int nt = ctx->n_theta_I, np = ctx->n_phi_I, ntf = ctx->rt2_N_type_flux, nc = ctx->M.n_cells;
   const size_t n = (size_t)ntf * nt * np * nc;
-  DevBuf<double> d_in;
-  HIPCHK(d_in.alloc(n)); HIPCHK(d_in.put(I_spec, n));
+  DevArr<double> d_in;
+  HIPCHK(d_in.resize(n)); HIPCHK(d_in.put(I_spec, n));
   HIPCHK(hipMemsetAsync(ctx->d_I_spec, 0, (size_t)nc * np * nt * XI_LINE * sizeof(double), ctx->stream));
   hipLaunchKernelGGL(k_I_spec_put, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_I_spec, d_in.p, ntf, nt, np, n);
   HIPCHK(hipGetLastError());
@@ -2590,26 +2551,23 @@ extern "C" int mcgpu_rt2_source(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, int p_la
           }
         }
     }
-  DevBuf<int> d_k;
-  DevBuf<float> d_sin, d_T;
-  DevBuf<double> d_cw, d_sw, d_J, d_rg, d_zg;
-  HIPCHK(d_k.alloc(tab_k.size())); HIPCHK(d_k.put(tab_k.data(), tab_k.size()));
-  HIPCHK(d_sin.alloc(tab_sin.size())); HIPCHK(d_sin.put(tab_sin.data(), tab_sin.size()));
-  HIPCHK(d_cw.alloc(ntab)); HIPCHK(d_cw.put(tab_cosw.data(), ntab));
-  HIPCHK(d_sw.alloc(ntab)); HIPCHK(d_sw.put(tab_sinw.data(), ntab));
-  HIPCHK(d_T.alloc(M.n_cells)); HIPCHK(d_T.put(Tdust, M.n_cells));
-  HIPCHK(d_J.alloc(M.n_cells));
-  HIPCHK(d_rg.alloc(M.n_cells)); HIPCHK(d_rg.put(r_grid, M.n_cells));
-  HIPCHK(d_zg.alloc(M.n_cells)); HIPCHK(d_zg.put(z_grid, M.n_cells));
+  DevArr<int> d_k;
+  DevArr<float> d_sin, d_T;
+  DevArr<double> d_cw, d_sw, d_J, d_rg, d_zg;
+  HIPCHK(d_k.resize(tab_k.size())); HIPCHK(d_k.put(tab_k.data(), tab_k.size()));
+  HIPCHK(d_sin.resize(tab_sin.size())); HIPCHK(d_sin.put(tab_sin.data(), tab_sin.size()));
+  HIPCHK(d_cw.resize(ntab)); HIPCHK(d_cw.put(tab_cosw.data(), ntab));
+  HIPCHK(d_sw.resize(ntab)); HIPCHK(d_sw.put(tab_sinw.data(), ntab));
+  HIPCHK(d_T.resize(M.n_cells)); HIPCHK(d_T.put(Tdust, M.n_cells));
+  HIPCHK(d_J.resize(M.n_cells));
+  HIPCHK(d_rg.resize(M.n_cells)); HIPCHK(d_rg.put(r_grid, M.n_cells));
+  HIPCHK(d_zg.resize(M.n_cells)); HIPCHK(d_zg.put(z_grid, M.n_cells));
   const size_t n_eps = (size_t)ntf * na * 2 * M.n_cells, n_eps_s = (size_t)n_Stokes * ns * 2 * M.n_cells;
   // (the result stays in HBM for mcgpu_rt2_dust_map / mcgpu_rt2_image)
-  if (ctx->d_eps2) hipFree(ctx->d_eps2);
-  if (ctx->d_eps2_star) hipFree(ctx->d_eps2_star);
-  if (ctx->d_rt2_zgrid) hipFree(ctx->d_rt2_zgrid);
-  ctx->d_eps2 = ctx->d_eps2_star = nullptr; ctx->d_rt2_zgrid = nullptr; ctx->rt2_src_ibin = 0;
-  HIPCHK(hipMalloc((void**)&ctx->d_eps2, n_eps * sizeof(float)));
-  HIPCHK(hipMalloc((void**)&ctx->d_eps2_star, n_eps_s * sizeof(float)));
-  HIPCHK(hipMalloc((void**)&ctx->d_rt2_zgrid, (size_t)M.n_cells * sizeof(double)));
+  ctx->d_eps2.reset(); ctx->d_eps2_star.reset(); ctx->d_rt2_zgrid.reset(); ctx->rt2_src_ibin = 0;
+  HIPCHK(ctx->d_eps2.resize(n_eps));
+  HIPCHK(ctx->d_eps2_star.resize(n_eps_s));
+  HIPCHK(ctx->d_rt2_zgrid.resize((size_t)M.n_cells));
   HIPCHK(hipMemcpyAsync(ctx->d_rt2_zgrid, z_grid, (size_t)M.n_cells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   Rt2Args A;
   std::memset(&A, 0, sizeof(A));
@@ -2659,33 +2617,29 @@ static bool xi_log_applicable(const mcgpu_ctx* ctx, bool rt1) {
 // (Measured and dropped, profiles/r06_xi_log_ab.log: two buffer sets with the sort and the fold of launch i on a second
 // stream under launch i + 1's transport -- the persistent transport kernel leaves them a wave per SIMD, the sort ran 4x
 // slower, and the sum stayed what it was.)
+static inline size_t xlog_cap(const mcgpu_ctx* ctx) { return ctx->d_xlog_temp ? ctx->d_xlog_keys[0].n : 0; }                               // records
+static inline size_t xlog_rows_cap(const mcgpu_ctx* ctx) { return ctx->d_xlog_temp ? ctx->d_xlog_rows.n / ctx->xlog_row_floats : 0; }   // flights
+
 static int xi_log_prepare(mcgpu_ctx* ctx, unsigned long long n_items, int nRT, bool pola) {
   const size_t row_floats = (size_t)nRT * (pola ? 4 : 1);
   size_t cap = (size_t)1 << 28, rows = (size_t)1 << 26;
   // (a run of few packets -- the tests' -- does not need gigabytes: ~4096 crossings and 1024 flights per packet are provided for)
   while (cap > ((size_t)1 << 22) && (double)cap > 4096.0 * (double)n_items + 8.0e6) cap >>= 1;
   while (rows > ((size_t)1 << 20) && (double)rows > 1024.0 * (double)n_items + 2.0e6) rows >>= 1;
-  if (ctx->xlog_cap >= cap && ctx->xlog_rows_cap >= rows && ctx->xlog_row_floats == row_floats) return MCGPU_OK;
-  if (ctx->xlog_cap > cap) cap = ctx->xlog_cap;
-  if (ctx->xlog_rows_cap > rows && ctx->xlog_row_floats == row_floats) rows = ctx->xlog_rows_cap;
+  if (xlog_cap(ctx) >= cap && xlog_rows_cap(ctx) >= rows && ctx->xlog_row_floats == row_floats) return MCGPU_OK;
+  if (xlog_cap(ctx) > cap) cap = xlog_cap(ctx);
+  if (xlog_rows_cap(ctx) > rows && ctx->xlog_row_floats == row_floats) rows = xlog_rows_cap(ctx);
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (int i = 0; i < 2; ++i) {
-    if (ctx->d_xlog_keys[i]) hipFree(ctx->d_xlog_keys[i]);
-    if (ctx->d_xlog_vals[i]) hipFree(ctx->d_xlog_vals[i]);
-    ctx->d_xlog_keys[i] = nullptr; ctx->d_xlog_vals[i] = nullptr;
-  }
-  if (ctx->d_xlog_rows) hipFree(ctx->d_xlog_rows);
-  if (ctx->d_xlog_temp) hipFree(ctx->d_xlog_temp);
-  ctx->d_xlog_rows = nullptr; ctx->d_xlog_temp = nullptr; ctx->xlog_cap = 0; ctx->xlog_rows_cap = 0;
+  for (int i = 0; i < 2; ++i) { ctx->d_xlog_keys[i].reset(); ctx->d_xlog_vals[i].reset(); }
+  ctx->d_xlog_rows.reset(); ctx->d_xlog_temp.reset();
+  ctx->xlog_row_floats = row_floats;
   for (int i = 0; i < 2; ++i) {   // [0]: the launch's log; [1]: the sorted copy
-    HIPCHK(hipMalloc((void**)&ctx->d_xlog_keys[i], cap * sizeof(unsigned int)));
-    HIPCHK(hipMalloc((void**)&ctx->d_xlog_vals[i], cap * sizeof(unsigned long long)));
+    HIPCHK(ctx->d_xlog_keys[i].resize(cap));
+    HIPCHK(ctx->d_xlog_vals[i].resize(cap));
   }
-  HIPCHK(hipMalloc((void**)&ctx->d_xlog_rows, rows * row_floats * sizeof(float)));
-  if (!ctx->d_xlog_ctl) HIPCHK(hipMalloc((void**)&ctx->d_xlog_ctl, 2 * sizeof(unsigned long long)));
-  ctx->xlog_temp_bytes = xi_sort_temp_bytes(cap, 31);
-  HIPCHK(hipMalloc(&ctx->d_xlog_temp, ctx->xlog_temp_bytes ? ctx->xlog_temp_bytes : 16));
-  ctx->xlog_cap = cap; ctx->xlog_rows_cap = rows; ctx->xlog_row_floats = row_floats;
+  HIPCHK(ctx->d_xlog_rows.resize(rows * row_floats));
+  HIPCHK(ctx->d_xlog_ctl.reserve(2));
+  HIPCHK(ctx->d_xlog_temp.resize(xi_sort_temp_bytes(cap, 31)));   // (the last one: with it the set is complete)
   return MCGPU_OK;
 }
 
@@ -2711,17 +2665,17 @@ static int commit_mono(mcgpu_ctx* ctx, MonoArgs A, int grid_blocks, int block_th
   while (end_bit < 31 && (1u << end_bit) <= n_bins) ++end_bit;   // the unused entries' key, 2^end_bit - 1 >= n_bins, sorts last
   if ((1u << end_bit) - 1u < n_bins) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "xI log: too many sub-bins for a 31-bit key");
   A.log_keys = ctx->d_xlog_keys[0]; A.log_vals = ctx->d_xlog_vals[0]; A.log_rows = ctx->d_xlog_rows; A.log_ctl = ctx->d_xlog_ctl;
-  A.log_cap = ctx->xlog_cap; A.rows_cap = ctx->xlog_rows_cap; A.log_sentinel = (1u << end_bit) - 1u;
+  A.log_cap = xlog_cap(ctx); A.rows_cap = xlog_rows_cap(ctx); A.log_sentinel = (1u << end_bit) - 1u;
   const int nv = pola ? 4 : 1;
   // (the first launch: room for 1024 records and 256 flights per packet -- ref4.1 has 60-160 and 2-60, by wavelength)
   unsigned long long done = 0, chunk = 1000000ull;
-  if (chunk > ctx->xlog_cap / 1024) chunk = ctx->xlog_cap / 1024;
-  if (chunk > ctx->xlog_rows_cap / 256) chunk = ctx->xlog_rows_cap / 256;
+  if (chunk > xlog_cap(ctx) / 1024) chunk = xlog_cap(ctx) / 1024;
+  if (chunk > xlog_rows_cap(ctx) / 256) chunk = xlog_rows_cap(ctx) / 256;
   double rpp = 0.0, fpp = 0.0;   // records / flights reserved per packet, as measured
   while (done < n_total) {
     if (rpp > 0.0) {
-      double c = 0.7 * (double)ctx->xlog_cap / rpp;
-      if (fpp > 0.0 && 0.7 * (double)ctx->xlog_rows_cap / fpp < c) c = 0.7 * (double)ctx->xlog_rows_cap / fpp;
+      double c = 0.7 * (double)xlog_cap(ctx) / rpp;
+      if (fpp > 0.0 && 0.7 * (double)xlog_rows_cap(ctx) / fpp < c) c = 0.7 * (double)xlog_rows_cap(ctx) / fpp;
       chunk = c < 1024.0 ? 1024ull : (unsigned long long)c;
     }
     const unsigned long long c = chunk < n_total - done ? chunk : n_total - done;
@@ -2734,16 +2688,16 @@ static int commit_mono(mcgpu_ctx* ctx, MonoArgs A, int grid_blocks, int block_th
     HIPCHK(hipMemcpyAsync(ctl, ctx->d_xlog_ctl, sizeof(ctl), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(&dev_err, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));   // (the host needs the record count for the sort)
-    if (dev_err == 18 || ctl[0] > ctx->xlog_cap || ctl[1] > ctx->xlog_rows_cap) {
+    if (dev_err == 18 || ctl[0] > xlog_cap(ctx) || ctl[1] > xlog_rows_cap(ctx)) {
       ctx->err = "xI log: a launch of " + std::to_string(c) + " packets logged " + std::to_string(ctl[0]) + " records and " + std::to_string(ctl[1]) +
-                 " flights, more than the buffers hold (" + std::to_string(ctx->xlog_cap) + ", " + std::to_string(ctx->xlog_rows_cap) +
+                 " flights, more than the buffers hold (" + std::to_string(xlog_cap(ctx)) + ", " + std::to_string(xlog_rows_cap(ctx)) +
                  "): mcgpu_set_option(ctx, \"xi_log\", 0) runs this model with atomics";
       return MCGPU_ERR_KERNEL;
     }
     if (dev_err) { ctx->err = "device error " + std::to_string(dev_err) + " in the commit pass"; return MCGPU_ERR_KERNEL; }
     const int e = xi_sort_fold(ctx->stream, ctx->d_xlog_keys[0], ctx->d_xlog_vals[0], ctx->d_xlog_keys[1], ctx->d_xlog_vals[1], (size_t)ctl[0],
-                               end_bit, ctx->d_xlog_temp, ctx->xlog_temp_bytes, ctx->d_xlog_rows, A.nRT, nv, A.contrib, n_bins,
-                               reinterpret_cast<float*>(ctx->d_xI), A.xi);
+                               end_bit, ctx->d_xlog_temp, ctx->d_xlog_temp.n, ctx->d_xlog_rows, A.nRT, nv, A.contrib, n_bins,
+                               reinterpret_cast<float*>(ctx->d_xI.p), A.xi);
     if (e != (int)hipSuccess) { ctx->err = std::string("xI log: sort / fold: ") + hipGetErrorString((hipError_t)e); return MCGPU_ERR_HIP; }
     rpp = (double)ctl[0] / (double)c; fpp = (double)ctl[1] / (double)c;
     ctx->xlog_chunks++; ctx->xlog_records += ctl[0]; ctx->xlog_flights += ctl[1];
@@ -2790,19 +2744,16 @@ extern "C" int mcgpu_run_mono(mcgpu_ctx* ctx, const mcgpu_mono_opts* o, double f
   HIPCHK(hipSetDevice(ctx->device));
   if ((rc = ensure_accum(ctx))) return rc;
   const int nc = o->n_chunks;
-  if (ctx->mono_chunks < nc) {
-    if (ctx->d_mono_u64) hipFree(ctx->d_mono_u64);
-    if (ctx->d_mono_i32) hipFree(ctx->d_mono_i32);
-    ctx->d_mono_u64 = nullptr; ctx->d_mono_i32 = nullptr; ctx->mono_chunks = 0;
-    HIPCHK(hipMalloc((void**)&ctx->d_mono_u64, ((size_t)5 * nc + 1) * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc((void**)&ctx->d_mono_i32, (size_t)2 * nc * sizeof(int)));
-    ctx->mono_chunks = nc;
+  if (ctx->d_mono_i32.n < (size_t)2 * nc) {   // (the second of the pair: sized for the most chunks asked for so far)
+    ctx->d_mono_u64.reset(); ctx->d_mono_i32.reset();
+    HIPCHK(ctx->d_mono_u64.resize((size_t)5 * nc + 1));
+    HIPCHK(ctx->d_mono_i32.resize((size_t)2 * nc));
   }
   unsigned long long *d_need = ctx->d_mono_u64, *d_sent = d_need + nc, *d_base = d_sent + nc;
   unsigned long long *d_start = d_base + nc + 1, *d_hitcnt = d_start + nc;
   int *d_active = ctx->d_mono_i32, *d_done = d_active + nc;
   if (prob_E_cell) {
-    if (!ctx->d_prob_E) HIPCHK(hipMalloc((void**)&ctx->d_prob_E, ((size_t)M.n_cells + 1) * sizeof(double)));
+    HIPCHK(ctx->d_prob_E.reserve((size_t)M.n_cells + 1));
     HIPCHK(hipMemcpyAsync(ctx->d_prob_E, prob_E_cell, ((size_t)M.n_cells + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     ctx->prob_E_lambda = 0;
   }
@@ -2812,9 +2763,8 @@ extern "C" int mcgpu_run_mono(mcgpu_ctx* ctx, const mcgpu_mono_opts* o, double f
   const size_t xi_bytes = rt1 ? xi_dev_bytes(ctx) : 0;
   if (rt1 && ctx->N_type_flux > XI_LINE) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "N_type_flux > 8");
   if (rt1 && ctx->n_xI != n_xI) {
-    if (ctx->d_xI) hipFree(ctx->d_xI);
-    ctx->d_xI = nullptr; ctx->n_xI = 0;
-    HIPCHK(hipMalloc((void**)&ctx->d_xI, xi_bytes));
+    ctx->d_xI.reset(); ctx->n_xI = 0;
+    HIPCHK(ctx->d_xI.resize((xi_bytes + 7) / 8));
     ctx->n_xI = n_xI;
     HIPCHK(hipMemsetAsync(ctx->d_xI, 0, xi_bytes, ctx->stream));
   } else if (rt1 && !o->accumulate) {
@@ -2827,7 +2777,7 @@ extern "C" int mcgpu_run_mono(mcgpu_ctx* ctx, const mcgpu_mono_opts* o, double f
   // (the E_abs part of the fused accumulator belongs to the thermal step: a host may run the SED Monte Carlo and
   // then call mcgpu_temp_finale(ctx, NULL, ...) on the device's own absorbed-energy grid)
   if (!o->accumulate) {
-    HIPCHK(hipMemsetAsync(ctx->d_accum + M.n_cells, 0, (ctx->n_accum - M.n_cells) * sizeof(double), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_accum + M.n_cells, 0, (ctx->d_accum.n - M.n_cells) * sizeof(double), ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_counters, 0, CNT_SLOTS * sizeof(unsigned long long), ctx->stream));
   }
   HIPCHK(hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream));
@@ -2896,12 +2846,7 @@ restart:
     if (b < 64.0) b = 64.0;
     const unsigned long long batch = ((unsigned long long)b + 63ull) / 64ull * 64ull;
     const size_t nh = (size_t)na * batch;
-    if (ctx->hits_cap < nh) {
-      if (ctx->d_hits) hipFree(ctx->d_hits);
-      ctx->d_hits = nullptr; ctx->hits_cap = 0;
-      HIPCHK(hipMalloc((void**)&ctx->d_hits, nh));
-      ctx->hits_cap = nh;
-    }
+    HIPCHK(ctx->d_hits.reserve(nh));
     HIPCHK(hipMemsetAsync(ctx->d_hits, 0, nh, ctx->stream));
     HIPCHK(hipMemcpyAsync(d_active, active.data(), na * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_counters + WORK_SLOT, 0, sizeof(unsigned long long), ctx->stream));
@@ -2963,7 +2908,7 @@ restart:
         for (int c : active) if (extra[c] > 0 && hc[c] >= o->n_photons2) overshoot = true;
         if (overshoot) {  // (a 7-sigma event) clear what this call accumulated and run it the plain way
           speculate = false;
-          HIPCHK(hipMemsetAsync(ctx->d_accum + M.n_cells, 0, (ctx->n_accum - M.n_cells) * sizeof(double), ctx->stream));
+          HIPCHK(hipMemsetAsync(ctx->d_accum + M.n_cells, 0, (ctx->d_accum.n - M.n_cells) * sizeof(double), ctx->stream));
           HIPCHK(hipMemsetAsync(ctx->d_counters, 0, CNT_SLOTS * sizeof(unsigned long long), ctx->stream));
           if (rt1) HIPCHK(hipMemsetAsync(ctx->d_xI, 0, xi_bytes, ctx->stream));
           if (rt2) {
@@ -3008,8 +2953,7 @@ extern "C" int mcgpu_set_xI_precision(mcgpu_ctx* ctx, int bytes_per_value) {
   if (bytes_per_value != 4 && bytes_per_value != 8) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_xI_precision: 4 or 8");
   if (bytes_per_value != ctx->xI_bytes) {
     hipSetDevice(ctx->device);
-    if (ctx->d_xI) hipFree(ctx->d_xI);  // the layout changes with the type: what was accumulated is dropped
-    ctx->d_xI = nullptr; ctx->n_xI = 0;
+    ctx->d_xI.reset(); ctx->n_xI = 0;  // the layout changes with the type: what was accumulated is dropped
     ctx->xI_bytes = bytes_per_value;
   }
   return MCGPU_OK;
@@ -3026,23 +2970,18 @@ extern "C" int mcgpu_set_xI(mcgpu_ctx* ctx, const double* xI_scatt) {
   const size_t n = (size_t)ctx->n_az_rt * ctx->n_theta_rt * ctx->N_type_flux * nRT * (size_t)ctx->M.n_cells;
   const size_t xi_bytes = xi_dev_bytes(ctx);
   if (ctx->n_xI != n) {
-    if (ctx->d_xI) hipFree(ctx->d_xI);
-    ctx->d_xI = nullptr; ctx->n_xI = 0;
-    HIPCHK(hipMalloc((void**)&ctx->d_xI, xi_bytes));
+    ctx->d_xI.reset(); ctx->n_xI = 0;
+    HIPCHK(ctx->d_xI.resize((xi_bytes + 7) / 8));
     ctx->n_xI = n;
   }
   HIPCHK(hipMemsetAsync(ctx->d_xI, 0, xi_bytes, ctx->stream));
-  double* d_in = nullptr;
-  HIPCHK(hipMalloc((void**)&d_in, n * sizeof(double)));
-  hipError_t e = hipMemcpyAsync(d_in, xI_scatt, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_xI_put, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_xI, d_in,
-                       ctx->n_az_rt, ctx->n_theta_rt, ctx->N_type_flux, nRT, n, ctx->xI_bytes == 4 ? 1 : 0, xi_layout_of(ctx), ctx->lsepar_pola ? 4 : 1);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(d_in);
-  HIPCHK(e);
+  DevArr<double> d_in;
+  HIPCHK(d_in.resize(n));
+  HIPCHK(hipMemcpyAsync(d_in, xI_scatt, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_xI_put, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_xI, d_in,
+                     ctx->n_az_rt, ctx->n_theta_rt, ctx->N_type_flux, nRT, n, ctx->xI_bytes == 4 ? 1 : 0, xi_layout_of(ctx), ctx->lsepar_pola ? 4 : 1);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return MCGPU_OK;
 }
 
@@ -3050,23 +2989,17 @@ extern "C" int mcgpu_fetch_xI(mcgpu_ctx* ctx, float* xI_scatt_f32, double* xI_sc
   if (!ctx || !ctx->d_xI) return fail(ctx, MCGPU_ERR_STATE, "no xI_scatt accumulated yet");
   HIPCHK(hipSetDevice(ctx->device));
   const size_t n = ctx->n_xI;
-  float* d32 = nullptr;
-  double* d64 = nullptr;
-  hipError_t e = hipSuccess;
-  if (xI_scatt_f32) e = hipMalloc((void**)&d32, n * sizeof(float));
-  if (e == hipSuccess && xI_scatt_f64) e = hipMalloc((void**)&d64, n * sizeof(double));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_xI_fetch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_xI, d32, d64,
-                       ctx->n_az_rt, ctx->n_theta_rt, ctx->N_type_flux, ctx->RT_n_incl * ctx->RT_n_az, n,
-                       ctx->xI_bytes == 4 ? 1 : 0, xi_layout_of(ctx), ctx->lsepar_pola ? 4 : 1);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && d32) e = hipMemcpyAsync(xI_scatt_f32, d32, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && d64) e = hipMemcpyAsync(xI_scatt_f64, d64, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (d32) hipFree(d32);
-  if (d64) hipFree(d64);
-  HIPCHK(e);
+  DevArr<float> d32;
+  DevArr<double> d64;
+  if (xI_scatt_f32) HIPCHK(d32.resize(n));
+  if (xI_scatt_f64) HIPCHK(d64.resize(n));
+  hipLaunchKernelGGL(k_xI_fetch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_xI, d32, d64,
+                     ctx->n_az_rt, ctx->n_theta_rt, ctx->N_type_flux, ctx->RT_n_incl * ctx->RT_n_az, n,
+                     ctx->xI_bytes == 4 ? 1 : 0, xi_layout_of(ctx), ctx->lsepar_pola ? 4 : 1);
+  HIPCHK(hipGetLastError());
+  if (d32) HIPCHK(hipMemcpyAsync(xI_scatt_f32, d32, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (d64) HIPCHK(hipMemcpyAsync(xI_scatt_f64, d64, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return MCGPU_OK;
 }
 
@@ -3076,25 +3009,23 @@ extern "C" int mcgpu_temp_finale(mcgpu_ctx* ctx, const double* E_abs, float* Tdu
   if (!Tdust) return fail(ctx, MCGPU_ERR_ARG, "null Tdust");
   HIPCHK(hipSetDevice(ctx->device));
   const DevModel& M = ctx->M;
-  double* d_E = nullptr;
+  DevArr<double> d_E;
   const double* src = ctx->d_accum;
   if (E_abs) {
-    HIPCHK(hipMalloc((void**)&d_E, (size_t)M.n_cells * sizeof(double)));
+    HIPCHK(d_E.resize((size_t)M.n_cells));
     HIPCHK(hipMemcpyAsync(d_E, E_abs, (size_t)M.n_cells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     src = d_E;
   } else if (!src) {
     return fail(ctx, MCGPU_ERR_STATE, "no accumulator to reduce");
   }
-  float* d_T = nullptr;
-  HIPCHK(hipMalloc((void**)&d_T, (size_t)M.n_cells * sizeof(float)));
+  DevArr<float> d_T;
+  HIPCHK(d_T.resize((size_t)M.n_cells));
   const int threads = 256, blocks = (M.n_cells + threads - 1) / threads;
   hipLaunchKernelGGL(k_temp_finale, dim3(blocks), dim3(threads), 0, ctx->stream, M, src, ctx->d_tab_Temp,
                      ctx->T_min, d_T);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(Tdust, d_T, (size_t)M.n_cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  hipFree(d_T);
-  if (d_E) hipFree(d_E);
   return MCGPU_OK;
 }
 
@@ -3103,20 +3034,14 @@ extern "C" int mcgpu_temp_finale(mcgpu_ctx* ctx, const double* E_abs, float* Tdu
 // ---------------------------------------------------------------------------------------------
 static void nlte_release(mcgpu_ctx* ctx, bool all) {
   auto& n = ctx->nl;
-  void* p[] = {n.d_Cabs, n.d_kcdf, n.d_proba, n.d_dens, n.d_lE, n.d_cdf};
-  for (void* q : p) if (q) hipFree(q);
-  n.d_Cabs = nullptr; n.d_kcdf = n.d_proba = n.d_dens = n.d_lE = n.d_cdf = nullptr;
+  n.d_Cabs.reset(); n.d_kcdf.reset(); n.d_proba.reset(); n.d_dens.reset(); n.d_lE.reset(); n.d_cdf.reset();
   n.n_grains = 0; n.mixed = false; n.tables_pending = false;
   // (the grains' temperatures of mcgpu_set_Tdust_1grain belong to these tables: the term of mcgpu_repartition_energie reads
   // C_abs_norm with them, so it goes when they go)
-  if (n.d_T1) hipFree(n.d_T1);
-  if (n.d_T1_dens) hipFree(n.d_T1_dens);
-  n.d_T1 = nullptr; n.d_T1_dens = nullptr; n.T1_grains = 0;
+  n.d_T1.reset(); n.d_T1_dens.reset(); n.T1_grains = 0;
   if (all) {
-    void* r[] = {n.d_J0, n.d_xJ, n.d_stats};
-    for (void* q : r) if (q) hipFree(q);
-    n.J0_n = n.xJ_n = 0;
-    n.d_J0 = n.d_xJ = nullptr; n.d_stats = nullptr; n.xJ_last = false;
+    n.d_J0.reset(); n.d_xJ.reset(); n.d_stats.reset();
+    n.xJ_last = false;
   }
 }
 
@@ -3128,9 +3053,9 @@ static int nlte_no_ctx() {
 }
 
 template <typename Tp>
-static hipError_t nlte_put(Tp** d, const Tp* h, size_t n) {
-  hipError_t e = hipMalloc((void**)d, (n ? n : 1) * sizeof(Tp));
-  if (e == hipSuccess) e = hipMemcpy(*d, h, n * sizeof(Tp), hipMemcpyHostToDevice);
+static hipError_t nlte_put(DevArr<Tp>& d, const Tp* h, size_t n) {
+  hipError_t e = d.resize(n);
+  if (e == hipSuccess) e = d.put(h, n);
   return e;
 }
 
@@ -3177,12 +3102,12 @@ extern "C" int mcgpu_set_nlte(mcgpu_ctx* ctx, int n_grains_nlte, int n_grains_nR
   std::vector<float> C((size_t)ng * nl);   // (k, lambda) -> [k][lambda]
   for (int l = 0; l < nl; ++l)
     for (int k = 0; k < ng; ++k) C[(size_t)k * nl + l] = C_abs_norm[(size_t)k + (size_t)ng * l];
-  hipError_t e = nlte_put(&n.d_Cabs, C.data(), C.size());
-  if (e == hipSuccess) e = nlte_put(&n.d_kcdf, kabs_nLTE_CDF, (size_t)(ng + 1) * nl);
-  if (e == hipSuccess && Proba_abs_RE_LTE) e = nlte_put(&n.d_proba, Proba_abs_RE_LTE, (size_t)nc * nl);
-  if (e == hipSuccess && grain_density) e = nlte_put(&n.d_dens, grain_density, (size_t)nc * ng);
-  if (e == hipSuccess) e = hipMalloc((void**)&n.d_lE, (size_t)ng * nT * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&n.d_cdf, (size_t)ng * nT * nl * sizeof(double));
+  hipError_t e = nlte_put(n.d_Cabs, C.data(), C.size());
+  if (e == hipSuccess) e = nlte_put(n.d_kcdf, kabs_nLTE_CDF, (size_t)(ng + 1) * nl);
+  if (e == hipSuccess && Proba_abs_RE_LTE) e = nlte_put(n.d_proba, Proba_abs_RE_LTE, (size_t)nc * nl);
+  if (e == hipSuccess && grain_density) e = nlte_put(n.d_dens, grain_density, (size_t)nc * ng);
+  if (e == hipSuccess) e = n.d_lE.resize((size_t)ng * nT);
+  if (e == hipSuccess) e = n.d_cdf.resize((size_t)ng * nT * nl);
   if (e == hipSuccess && log_E_em_1grain) {
     std::vector<double> lE((size_t)ng * nT), cdf((size_t)ng * nT * nl);   // (k, T) -> [k][T]; (lambda, k, T) -> [k][T][lambda]
     for (int t = 0; t < nT; ++t)
@@ -3218,8 +3143,8 @@ extern "C" int mcgpu_init_reemission_nlte(mcgpu_ctx* ctx, const double* tab_lamb
   for (int l = 0; l < nl; ++l)
     if (!(tab_lambda[l] > 0.0) || !(tab_delta_lambda[l] > 0.0))
       return fail(ctx, MCGPU_ERR_ARG, "mcgpu_init_reemission_nlte: wavelengths and bin widths must be positive");
-  DevBuf<double> d_lam;
-  HIPCHK(d_lam.alloc(2 * (size_t)nl));
+  DevArr<double> d_lam;
+  HIPCHK(d_lam.resize(2 * (size_t)nl));
   HIPCHK(hipMemcpy(d_lam.p, tab_lambda, (size_t)nl * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d_lam.p + nl, tab_delta_lambda, (size_t)nl * sizeof(double), hipMemcpyHostToDevice));
   {
@@ -3266,11 +3191,9 @@ extern "C" int mcgpu_set_J0(mcgpu_ctx* ctx, const double* J0) {
   if (!ctx->have_grid || !ctx->have_opacity) return fail(ctx, MCGPU_ERR_STATE, "mcgpu_set_J0: set the grid and the opacities first");
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->nl.d_J0) { hipFree(ctx->nl.d_J0); ctx->nl.d_J0 = nullptr; }
-  ctx->nl.J0_n = 0;
+  ctx->nl.d_J0.reset();
   if (!J0) return MCGPU_OK;
-  ctx->nl.J0_n = (size_t)ctx->M.n_cells * nlte_ldJ(ctx->M.n_lambda);
-  HIPCHK(hipMalloc((void**)&ctx->nl.d_J0, ctx->nl.J0_n * sizeof(double)));
+  HIPCHK(ctx->nl.d_J0.resize((size_t)ctx->M.n_cells * nlte_ldJ(ctx->M.n_lambda)));
   HIPCHK(nlte_put_field(ctx, J0, ctx->nl.d_J0));
   return MCGPU_OK;
 }
@@ -3286,7 +3209,7 @@ static int nlte_scope(mcgpu_ctx* ctx) {
   if (M.mrw) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "non-LTE grains with the modified random walk are not built");
   if (ctx->nl.n_grains && (ctx->nl.dim_lambda != M.n_lambda || ctx->nl.dim_T != M.n_T || ctx->nl.dim_cells != M.n_cells))
     return fail(ctx, MCGPU_ERR_STATE, "the non-LTE tables were set for another grid, wavelength or temperature sampling: mcgpu_set_nlte again");
-  if (ctx->nl.d_J0 && ctx->nl.J0_n != (size_t)M.n_cells * nlte_ldJ(M.n_lambda))
+  if (ctx->nl.d_J0 && ctx->nl.d_J0.n != (size_t)M.n_cells * nlte_ldJ(M.n_lambda))
     return fail(ctx, MCGPU_ERR_STATE, "J0 was set for another grid or wavelength sampling: mcgpu_set_J0 again");
   if (ctx->nl.tables_pending)
     return fail(ctx, MCGPU_ERR_STATE, "the per-grain re-emission tables were left to mcgpu_init_reemission_nlte: call it first");
@@ -3299,9 +3222,8 @@ static int launch_nlte(mcgpu_ctx* ctx, RunArgs A, const mcgpu_run_opts* o) {
   if (rc) return rc;
   const DevModel& M = ctx->M;
   const size_t nj = (size_t)M.n_cells * nlte_ldJ(M.n_lambda);
-  if (ctx->nl.d_xJ && ctx->nl.xJ_n != nj) { hipFree(ctx->nl.d_xJ); ctx->nl.d_xJ = nullptr; }
-  if (!ctx->nl.d_xJ) { HIPCHK(hipMalloc((void**)&ctx->nl.d_xJ, nj * sizeof(double))); HIPCHK(hipMemset(ctx->nl.d_xJ, 0, nj * sizeof(double))); ctx->nl.xJ_n = nj; }
-  if (!ctx->nl.d_stats) HIPCHK(hipMalloc((void**)&ctx->nl.d_stats, 2 * sizeof(unsigned long long)));
+  if (!ctx->nl.d_xJ || ctx->nl.d_xJ.n != nj) { HIPCHK(ctx->nl.d_xJ.resize(nj)); HIPCHK(hipMemset(ctx->nl.d_xJ, 0, nj * sizeof(double))); }
+  HIPCHK(ctx->nl.d_stats.reserve(2));
   if (!o->accumulate) HIPCHK(hipMemsetAsync(ctx->nl.d_xJ, 0, nj * sizeof(double), ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->nl.d_stats, 0, 2 * sizeof(unsigned long long), ctx->stream));
   A.xJ_abs = nullptr;   // (the launch keeps xJ_abs itself, a cell's wavelengths contiguous: N.xJ)
@@ -3339,17 +3261,17 @@ extern "C" int mcgpu_temp_finale_nlte(mcgpu_ctx* ctx, const double* xJ_abs, floa
   HIPCHK(hipStreamSynchronize(ctx->stream));
   const DevModel& M = ctx->M;
   NlteArgs N = nlte_args(ctx);
-  DevBuf<double> d_x;
+  DevArr<double> d_x;
   if (xJ_abs) {
-    HIPCHK(d_x.alloc((size_t)M.n_cells * N.ldJ));
+    HIPCHK(d_x.resize((size_t)M.n_cells * N.ldJ));
     HIPCHK(nlte_put_field(ctx, xJ_abs, d_x.p));
     N.xJ = d_x.p;
-  } else if (!ctx->nl.d_xJ || ctx->nl.xJ_n != (size_t)M.n_cells * N.ldJ) {
+  } else if (!ctx->nl.d_xJ || ctx->nl.d_xJ.n != (size_t)M.n_cells * N.ldJ) {
     return fail(ctx, MCGPU_ERR_STATE, "no xJ_abs to reduce: no non-LTE launch on this model yet");
   }
   const size_t nout = (size_t)M.n_cells * N.n_grains;
-  DevBuf<float> d_T;
-  HIPCHK(d_T.alloc(nout));
+  DevArr<float> d_T;
+  HIPCHK(d_T.resize(nout));
   const double* vol = M.volume;
   float T_min = ctx->T_min;
   float* out = d_T.p;
@@ -3364,8 +3286,7 @@ extern "C" int mcgpu_set_Tdust_1grain(mcgpu_ctx* ctx, const float* Tdust_1grain,
   if (!ctx) return nlte_no_ctx();
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->nl.d_T1) { hipFree(ctx->nl.d_T1); ctx->nl.d_T1 = nullptr; }
-  if (ctx->nl.d_T1_dens) { hipFree(ctx->nl.d_T1_dens); ctx->nl.d_T1_dens = nullptr; }
+  ctx->nl.d_T1.reset(); ctx->nl.d_T1_dens.reset();
   ctx->nl.T1_grains = 0;
   if (!Tdust_1grain) return MCGPU_OK;   // (off again)
   if (!grain_density) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_Tdust_1grain: the grains' densities are needed");
@@ -3373,9 +3294,8 @@ extern "C" int mcgpu_set_Tdust_1grain(mcgpu_ctx* ctx, const float* Tdust_1grain,
   if (ctx->nl.dim_lambda != ctx->M.n_lambda || ctx->nl.dim_cells != ctx->M.n_cells)
     return fail(ctx, MCGPU_ERR_STATE, "mcgpu_set_Tdust_1grain: the non-LTE tables were set for another grid or wavelength sampling");
   const size_t n = (size_t)ctx->M.n_cells * ctx->nl.n_grains;
-  hipError_t e = nlte_put(&ctx->nl.d_T1, Tdust_1grain, n);
-  if (e == hipSuccess) e = nlte_put(&ctx->nl.d_T1_dens, grain_density, n);
-  if (e != hipSuccess) return fail(ctx, MCGPU_ERR_HIP, hipGetErrorString(e));
+  HIPCHK(nlte_put(ctx->nl.d_T1, Tdust_1grain, n));
+  HIPCHK(nlte_put(ctx->nl.d_T1_dens, grain_density, n));
   ctx->nl.T1_grains = ctx->nl.n_grains;
   return MCGPU_OK;
 }
@@ -3395,10 +3315,10 @@ extern "C" int mcgpu_probe_reemission_nlte(mcgpu_ctx* ctx, int n, const int* ice
   if (!n) return MCGPU_OK;
   HIPCHK(hipSetDevice(ctx->device));
   NlteArgs N = nlte_args(ctx);
-  DevBuf<int> d_i, d_o;
-  DevBuf<float> d_r;
-  DevBuf<double> d_T;
-  HIPCHK(d_i.alloc(2 * (size_t)n)); HIPCHK(d_o.alloc(3 * (size_t)n)); HIPCHK(d_r.alloc(2 * (size_t)n)); HIPCHK(d_T.alloc((size_t)n));
+  DevArr<int> d_i, d_o;
+  DevArr<float> d_r;
+  DevArr<double> d_T;
+  HIPCHK(d_i.resize(2 * (size_t)n)); HIPCHK(d_o.resize(3 * (size_t)n)); HIPCHK(d_r.resize(2 * (size_t)n)); HIPCHK(d_T.resize((size_t)n));
   HIPCHK(hipMemcpy(d_i.p, icell, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d_i.p + n, lambda0, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d_r.p, rand1, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
@@ -3434,14 +3354,14 @@ extern "C" int mcgpu_temp_approx_diffusion_vertical(mcgpu_ctx* ctx, const double
   for (int i = 0; i < M.n_rad; ++i)
     if (zj_sup_dark_zone[i] < 0 || zj_sup_dark_zone[i] > M.nz) return fail(ctx, MCGPU_ERR_ARG, "zj_sup_dark_zone out of range");
   HIPCHK(hipSetDevice(ctx->device));
-  DevBuf<double> d_lam, d_dl;
-  DevBuf<int> d_zj, d_it;
-  DevBuf<float> d_T;
-  HIPCHK(d_lam.alloc(M.n_lambda)); HIPCHK(d_lam.put(tab_lambda, M.n_lambda));
-  HIPCHK(d_dl.alloc(M.n_lambda)); HIPCHK(d_dl.put(tab_delta_lambda, M.n_lambda));
-  HIPCHK(d_zj.alloc(M.n_rad)); HIPCHK(d_zj.put(zj_sup_dark_zone, M.n_rad));
-  HIPCHK(d_it.alloc(1)); HIPCHK(hipMemset(d_it.p, 0, sizeof(int)));
-  HIPCHK(d_T.alloc(M.n_cells)); HIPCHK(d_T.put(Tdust, M.n_cells));
+  DevArr<double> d_lam, d_dl;
+  DevArr<int> d_zj, d_it;
+  DevArr<float> d_T;
+  HIPCHK(d_lam.resize(M.n_lambda)); HIPCHK(d_lam.put(tab_lambda, M.n_lambda));
+  HIPCHK(d_dl.resize(M.n_lambda)); HIPCHK(d_dl.put(tab_delta_lambda, M.n_lambda));
+  HIPCHK(d_zj.resize(M.n_rad)); HIPCHK(d_zj.put(zj_sup_dark_zone, M.n_rad));
+  HIPCHK(d_it.resize(1)); HIPCHK(hipMemset(d_it.p, 0, sizeof(int)));
+  HIPCHK(d_T.resize(M.n_cells)); HIPCHK(d_T.put(Tdust, M.n_cells));
   HIPCHK(hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream));
   if (ri_out_dark_zone >= ri_in_dark_zone) {
     hipLaunchKernelGGL(k_clean_dark_temperature, dim3(ri_out_dark_zone - ri_in_dark_zone + 1), dim3(64), 0, ctx->stream,
@@ -3471,8 +3391,8 @@ extern "C" int mcgpu_temp_approx_diffusion_vertical(mcgpu_ctx* ctx, const double
 // ---------------------------------------------------------------------------------------------
 // common part of the two entry points: checks, J_th, the RtArgs both kernels share
 struct Rt1Job {
-  DevBuf<float> d_T, d_az;
-  DevBuf<double> d_J;
+  DevArr<float> d_T, d_az;
+  DevArr<double> d_J;
   RtArgs A;
   bool method2 = false;
 };
@@ -3496,9 +3416,9 @@ static int rt1_prepare(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, const float* tab_
     return fail(ctx, MCGPU_ERR_ARG, who);
   HIPCHK(hipSetDevice(ctx->device));
   const int nRT = ctx->RT_n_incl * ctx->RT_n_az;
-  HIPCHK(J.d_T.alloc(M.n_cells)); HIPCHK(J.d_T.put(Tdust, M.n_cells));
-  HIPCHK(J.d_az.alloc(ctx->RT_n_az)); HIPCHK(J.d_az.put(tab_RT_az, ctx->RT_n_az));
-  HIPCHK(J.d_J.alloc(M.n_cells));
+  HIPCHK(J.d_T.resize(M.n_cells)); HIPCHK(J.d_T.put(Tdust, M.n_cells));
+  HIPCHK(J.d_az.resize(ctx->RT_n_az)); HIPCHK(J.d_az.put(tab_RT_az, ctx->RT_n_az));
+  HIPCHK(J.d_J.resize(M.n_cells));
   RtArgs& A = J.A;
   std::memset(&A, 0, sizeof(A));
   A.lambda = o->lambda; A.RT_n_incl = ctx->RT_n_incl; A.nRT = nRT; A.n_az_rt = ctx->n_az_rt; A.n_theta_rt = ctx->n_theta_rt;
@@ -3562,8 +3482,8 @@ extern "C" int mcgpu_rt1_dust_map(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, const 
   int rc = rt1_prepare(ctx, o, tab_RT_az, Tdust, J, "mcgpu_rt1_dust_map: bad option");
   if (rc) return rc;
   const size_t n_out = (size_t)J.A.nRT * ctx->N_type_flux;
-  DevBuf<double> d_out;
-  HIPCHK(d_out.alloc(n_out));
+  DevArr<double> d_out;
+  HIPCHK(d_out.resize(n_out));
   HIPCHK(hipMemsetAsync(d_out.p, 0, n_out * sizeof(double), ctx->stream));
   J.A.out = d_out.p;
   const int n_rays = J.A.nRT * RT_N_RAD * RT_N_PHI;
@@ -3626,13 +3546,13 @@ extern "C" int mcgpu_define_dark_zone(mcgpu_ctx* ctx, int lambda, double tau_max
   std::memset(l_dark_zone, 0, (size_t)M.n_cells);
   const int i_lo = ri_in > 2 ? ri_in : 2, i_hi = ri_out;
   if (i_hi >= i_lo) {
-    DevBuf<int> d_zj;
-    DevBuf<double> d_rg, d_zg;
-    DevBuf<unsigned char> d_flag, d_now;
-    HIPCHK(d_zj.alloc(n_rad)); HIPCHK(d_zj.put(zj.data(), n_rad));
-    HIPCHK(d_rg.alloc(M.n_cells)); HIPCHK(d_rg.put(r_grid, M.n_cells));
-    HIPCHK(d_zg.alloc(M.n_cells)); HIPCHK(d_zg.put(z_grid, M.n_cells));
-    HIPCHK(d_flag.alloc(M.n_cells)); HIPCHK(d_now.alloc(M.n_cells));
+    DevArr<int> d_zj;
+    DevArr<double> d_rg, d_zg;
+    DevArr<unsigned char> d_flag, d_now;
+    HIPCHK(d_zj.resize(n_rad)); HIPCHK(d_zj.put(zj.data(), n_rad));
+    HIPCHK(d_rg.resize(M.n_cells)); HIPCHK(d_rg.put(r_grid, M.n_cells));
+    HIPCHK(d_zg.resize(M.n_cells)); HIPCHK(d_zg.put(z_grid, M.n_cells));
+    HIPCHK(d_flag.resize(M.n_cells)); HIPCHK(d_now.resize(M.n_cells));
     const long long n_rays = 11LL * (i_hi - i_lo + 1) * nz;
     const size_t lds = lds_bytes(M, true);
     HIPCHK(hipFuncSetAttribute((const void*)k_dark_zone_rays, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -3680,8 +3600,8 @@ extern "C" int mcgpu_rt2_dust_map(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, const 
   if (rc) return rc;
   const int ntf = ctx->rt2_N_type_flux;
   const size_t n_out = (size_t)J.A.nRT * ntf;
-  DevBuf<double> d_out;
-  HIPCHK(d_out.alloc(n_out));
+  DevArr<double> d_out;
+  HIPCHK(d_out.resize(n_out));
   HIPCHK(hipMemsetAsync(d_out.p, 0, n_out * sizeof(double), ctx->stream));
   J.A.out = d_out.p;
   const int n_rays = RT_N_RAD * RT_N_PHI;
@@ -3708,9 +3628,9 @@ extern "C" int mcgpu_rt2_image(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, const flo
   A.npix_x_max = o->l_sym_ima ? npix_x / 2 + npix_x % 2 : npix_x;
   A.taille_pix = (map_size / zoom) / (double)(npix_x > npix_y ? npix_x : npix_y);
   const size_t n_all = (size_t)A.nRT * ntf * npix_x * npix_y;
-  DevBuf<double> d_img;
-  DevBuf<unsigned long long> d_rays;
-  HIPCHK(d_img.alloc(n_all)); HIPCHK(d_rays.alloc(1));
+  DevArr<double> d_img;
+  DevArr<unsigned long long> d_rays;
+  HIPCHK(d_img.resize(n_all)); HIPCHK(d_rays.resize(1));
   HIPCHK(hipMemsetAsync(d_img.p, 0, n_all * sizeof(double), ctx->stream));
   HIPCHK(hipMemsetAsync(d_rays.p, 0, sizeof(unsigned long long), ctx->stream));
   A.image = d_img.p; A.n_rays = d_rays.p;
@@ -3741,17 +3661,17 @@ extern "C" int mcgpu_rt1_stars_map_sed(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, c
   if (o->lambda < 1 || o->lambda > M.n_lambda) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_rt1_stars_map_sed: bad option");
   HIPCHK(hipSetDevice(ctx->device));
   const int nRT = ctx->RT_n_incl * ctx->RT_n_az;
-  DevBuf<float> d_az;
-  DevBuf<double> d_flux, d_out;
-  HIPCHK(d_az.alloc(ctx->RT_n_az)); HIPCHK(d_az.put(tab_RT_az, ctx->RT_n_az));
-  HIPCHK(d_flux.alloc(M.n_stars)); HIPCHK(d_flux.put(star_flux, M.n_stars));
-  HIPCHK(d_out.alloc(nRT)); HIPCHK(hipMemsetAsync(d_out.p, 0, nRT * sizeof(double), ctx->stream));
+  DevArr<float> d_az;
+  DevArr<double> d_flux, d_out;
+  HIPCHK(d_az.resize(ctx->RT_n_az)); HIPCHK(d_az.put(tab_RT_az, ctx->RT_n_az));
+  HIPCHK(d_flux.resize(M.n_stars)); HIPCHK(d_flux.put(star_flux, M.n_stars));
+  HIPCHK(d_out.resize(nRT)); HIPCHK(hipMemsetAsync(d_out.p, 0, nRT * sizeof(double), ctx->stream));
   RtArgs A;
   std::memset(&A, 0, sizeof(A));
   A.lambda = o->lambda; A.RT_n_incl = ctx->RT_n_incl; A.nRT = nRT; A.ang_disque = o->ang_disque;
   A.rt_u = ctx->d_rt_u; A.rt_v = ctx->d_rt_v; A.rt_w = ctx->d_rt_w; A.rt_az = d_az.p;
-  DevBuf<VoroGrid> d_V;   // Voronoi grid: the kernels pick optical_length_tot_voro when they are handed the grid's record
-  if (ctx->voro) { HIPCHK(d_V.alloc(1)); HIPCHK(d_V.put(&ctx->V, 1)); A.voro = d_V.p; }
+  DevArr<VoroGrid> d_V;   // Voronoi grid: the kernels pick optical_length_tot_voro when they are handed the grid's record
+  if (ctx->voro) { HIPCHK(d_V.resize(1)); HIPCHK(d_V.put(&ctx->V, 1)); A.voro = d_V.p; }
   const size_t lds = lds_bytes(M, true);
   const unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
   if (M.l3D) {
@@ -3784,23 +3704,23 @@ extern "C" int mcgpu_rt1_stars_map_image(mcgpu_ctx* ctx, const mcgpu_rt_opts* o,
   const int nRT = ctx->RT_n_incl * ctx->RT_n_az;
   const int n_maps = (n_mu > 0 && pola_limb_darkening) ? 3 : 1;
   const size_t n_out = (size_t)npix_x * npix_y * n_maps * nRT;
-  DevBuf<float> d_az, d_mu, d_ld, d_pld;
-  DevBuf<double> d_flux, d_map, d_pos;
-  HIPCHK(d_az.alloc(ctx->RT_n_az)); HIPCHK(d_az.put(tab_RT_az, ctx->RT_n_az));
-  HIPCHK(d_flux.alloc(M.n_stars)); HIPCHK(d_flux.put(star_flux, M.n_stars));
-  HIPCHK(d_map.alloc(n_out)); HIPCHK(hipMemsetAsync(d_map.p, 0, n_out * sizeof(double), ctx->stream));
-  HIPCHK(d_pos.alloc((size_t)M.n_stars * nRT * 2));
+  DevArr<float> d_az, d_mu, d_ld, d_pld;
+  DevArr<double> d_flux, d_map, d_pos;
+  HIPCHK(d_az.resize(ctx->RT_n_az)); HIPCHK(d_az.put(tab_RT_az, ctx->RT_n_az));
+  HIPCHK(d_flux.resize(M.n_stars)); HIPCHK(d_flux.put(star_flux, M.n_stars));
+  HIPCHK(d_map.resize(n_out)); HIPCHK(hipMemsetAsync(d_map.p, 0, n_out * sizeof(double), ctx->stream));
+  HIPCHK(d_pos.resize((size_t)M.n_stars * nRT * 2));
   if (n_mu > 0) {
-    HIPCHK(d_mu.alloc(n_mu)); HIPCHK(d_mu.put(mu_limb_darkening, n_mu));
-    HIPCHK(d_ld.alloc(n_mu)); HIPCHK(d_ld.put(limb_darkening, n_mu));
-    if (pola_limb_darkening) { HIPCHK(d_pld.alloc(n_mu)); HIPCHK(d_pld.put(pola_limb_darkening, n_mu)); }
+    HIPCHK(d_mu.resize(n_mu)); HIPCHK(d_mu.put(mu_limb_darkening, n_mu));
+    HIPCHK(d_ld.resize(n_mu)); HIPCHK(d_ld.put(limb_darkening, n_mu));
+    if (pola_limb_darkening) { HIPCHK(d_pld.resize(n_mu)); HIPCHK(d_pld.put(pola_limb_darkening, n_mu)); }
   }
   RtArgs A;
   std::memset(&A, 0, sizeof(A));
   A.lambda = o->lambda; A.RT_n_incl = ctx->RT_n_incl; A.nRT = nRT; A.ang_disque = o->ang_disque;
   A.rt_u = ctx->d_rt_u; A.rt_v = ctx->d_rt_v; A.rt_w = ctx->d_rt_w; A.rt_az = d_az.p;
-  DevBuf<VoroGrid> d_V;   // Voronoi grid: the kernels pick optical_length_tot_voro when they are handed the grid's record
-  if (ctx->voro) { HIPCHK(d_V.alloc(1)); HIPCHK(d_V.put(&ctx->V, 1)); A.voro = d_V.p; }
+  DevArr<VoroGrid> d_V;   // Voronoi grid: the kernels pick optical_length_tot_voro when they are handed the grid's record
+  if (ctx->voro) { HIPCHK(d_V.resize(1)); HIPCHK(d_V.put(&ctx->V, 1)); A.voro = d_V.p; }
   StarsImageArgs I;
   I.npix_x = npix_x; I.npix_y = npix_y; I.n_maps = n_maps; I.n_mu = n_mu;
   I.taille_pix = (map_size / zoom) / (double)(npix_x > npix_y ? npix_x : npix_y);
@@ -3837,9 +3757,9 @@ extern "C" int mcgpu_rt1_image(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, const flo
   A.npix_x_max = o->l_sym_ima ? npix_x / 2 + npix_x % 2 : npix_x;               // dust_transfer.f90:1553-1557
   A.taille_pix = (map_size / zoom) / (double)(npix_x > npix_y ? npix_x : npix_y);  // (:1545)
   const size_t n_out = (size_t)A.nRT * ctx->N_type_flux * npix_x * npix_y;
-  DevBuf<double> d_img;
-  DevBuf<unsigned long long> d_rays;
-  HIPCHK(d_img.alloc(n_out)); HIPCHK(d_rays.alloc(1));
+  DevArr<double> d_img;
+  DevArr<unsigned long long> d_rays;
+  HIPCHK(d_img.resize(n_out)); HIPCHK(d_rays.resize(1));
   HIPCHK(hipMemsetAsync(d_img.p, 0, n_out * sizeof(double), ctx->stream));
   HIPCHK(hipMemsetAsync(d_rays.p, 0, sizeof(unsigned long long), ctx->stream));
   A.image = d_img.p; A.n_rays = d_rays.p;
@@ -3868,10 +3788,10 @@ extern "C" int mcgpu_tau_maps(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, const floa
   HIPCHK(hipSetDevice(ctx->device));
   const int nRT = ctx->RT_n_incl * ctx->RT_n_az;
   const size_t n_pix = (size_t)npix_x * npix_y * nRT;
-  DevBuf<float> d_az, d_tau, d_surf;
-  HIPCHK(d_az.alloc(ctx->RT_n_az)); HIPCHK(d_az.put(tab_RT_az, ctx->RT_n_az));
-  if (tau_map) HIPCHK(d_tau.alloc(n_pix));
-  if (tau_surface_map) HIPCHK(d_surf.alloc(3 * n_pix));
+  DevArr<float> d_az, d_tau, d_surf;
+  HIPCHK(d_az.resize(ctx->RT_n_az)); HIPCHK(d_az.put(tab_RT_az, ctx->RT_n_az));
+  if (tau_map) HIPCHK(d_tau.resize(n_pix));
+  if (tau_surface_map) HIPCHK(d_surf.resize(3 * n_pix));
   RtArgs A;
   std::memset(&A, 0, sizeof(A));
   A.lambda = o->lambda; A.RT_n_incl = ctx->RT_n_incl; A.nRT = nRT; A.ang_disque = o->ang_disque;
@@ -3910,12 +3830,12 @@ extern "C" int mcgpu_probe_cross_cell(mcgpu_ctx* ctx, int n, const double* x0, c
   if (ctx->voro) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "cylindrical probe on a Voronoi grid");
   HIPCHK(hipSetDevice(ctx->device));
   const DevModel& M = ctx->M;
-  DevBuf<double> in[6], out[4];
-  DevBuf<int> dc, dn;
+  DevArr<double> in[6], out[4];
+  DevArr<int> dc, dn;
   const double* hin[6] = {x0, y0, z0, u, v, w};
-  for (int q = 0; q < 6; ++q) { HIPCHK(in[q].alloc(n)); HIPCHK(in[q].put(hin[q], n)); }
-  for (int q = 0; q < 4; ++q) HIPCHK(out[q].alloc(n));
-  HIPCHK(dc.alloc(n)); HIPCHK(dc.put(cell, n)); HIPCHK(dn.alloc(n));
+  for (int q = 0; q < 6; ++q) { HIPCHK(in[q].resize(n)); HIPCHK(in[q].put(hin[q], n)); }
+  for (int q = 0; q < 4; ++q) HIPCHK(out[q].resize(n));
+  HIPCHK(dc.resize(n)); HIPCHK(dc.put(cell, n)); HIPCHK(dn.resize(n));
   const size_t lds = lds_bytes(M);
 #define PROBE_CROSS(a, b) do {                                                                                       \
     hipFuncSetAttribute((const void*)k_probe_cross<a, b>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
@@ -3942,14 +3862,14 @@ extern "C" int mcgpu_probe_cross_voronoi(mcgpu_ctx* ctx, int n, const double* x0
   if (rc) return rc;
   if (!ctx->voro) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "Voronoi probe on a cylindrical grid");
   HIPCHK(hipSetDevice(ctx->device));
-  DevBuf<double> in[6], out[6];
-  DevBuf<int> dc, dp, dn;
+  DevArr<double> in[6], out[6];
+  DevArr<int> dc, dp, dn;
   const double* hin[6] = {x0, y0, z0, u, v, w};
-  for (int q = 0; q < 6; ++q) { HIPCHK(in[q].alloc(n)); HIPCHK(in[q].put(hin[q], n)); }
-  for (int q = 0; q < 6; ++q) HIPCHK(out[q].alloc(n));
-  HIPCHK(dc.alloc(n)); HIPCHK(dc.put(cell, n));
-  HIPCHK(dp.alloc(n)); HIPCHK(dp.put(previous_cell, n));
-  HIPCHK(dn.alloc(n));
+  for (int q = 0; q < 6; ++q) { HIPCHK(in[q].resize(n)); HIPCHK(in[q].put(hin[q], n)); }
+  for (int q = 0; q < 6; ++q) HIPCHK(out[q].resize(n));
+  HIPCHK(dc.resize(n)); HIPCHK(dc.put(cell, n));
+  HIPCHK(dp.resize(n)); HIPCHK(dp.put(previous_cell, n));
+  HIPCHK(dn.resize(n));
   hipLaunchKernelGGL(k_probe_cross_voro, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->M, ctx->V, n,
                      in[0].p, in[1].p, in[2].p, in[3].p, in[4].p, in[5].p, dc.p, dp.p, out[0].p, out[1].p, out[2].p,
                      dn.p, out[3].p, out[4].p, out[5].p);
@@ -3968,11 +3888,11 @@ extern "C" int mcgpu_probe_index_cell(mcgpu_ctx* ctx, int n, const double* x, co
   if (ctx->voro) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "cylindrical probe on a Voronoi grid");
   HIPCHK(hipSetDevice(ctx->device));
   const DevModel& M = ctx->M;
-  DevBuf<double> in[3];
-  DevBuf<int> dn;
+  DevArr<double> in[3];
+  DevArr<int> dn;
   const double* hin[3] = {x, y, z};
-  for (int q = 0; q < 3; ++q) { HIPCHK(in[q].alloc(n)); HIPCHK(in[q].put(hin[q], n)); }
-  HIPCHK(dn.alloc(n));
+  for (int q = 0; q < 3; ++q) { HIPCHK(in[q].resize(n)); HIPCHK(in[q].put(hin[q], n)); }
+  HIPCHK(dn.resize(n));
   const size_t lds = lds_bytes(M);
 #define PROBE_INDEX(a, b) do {                                                                                       \
     hipFuncSetAttribute((const void*)k_probe_index<a, b>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
@@ -3990,8 +3910,8 @@ extern "C" int mcgpu_probe_index_cell(mcgpu_ctx* ctx, int n, const double* x, co
 extern "C" int mcgpu_probe_philox(mcgpu_ctx* ctx, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
   if (!ctx) return MCGPU_ERR_ARG;
   HIPCHK(hipSetDevice(ctx->device));
-  DevBuf<uint32_t> d;
-  HIPCHK(d.alloc(4));
+  DevArr<uint32_t> d;
+  HIPCHK(d.resize(4));
   hipLaunchKernelGGL(k_probe_philox, dim3(1), dim3(1), 0, ctx->stream, ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], d.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -4002,8 +3922,8 @@ extern "C" int mcgpu_probe_philox(mcgpu_ctx* ctx, const uint32_t ctr[4], const u
 extern "C" int mcgpu_probe_packet_rand(mcgpu_ctx* ctx, uint64_t seed, uint64_t packet, int n, float* out) {
   if (!ctx || n < 1) return MCGPU_ERR_ARG;
   HIPCHK(hipSetDevice(ctx->device));
-  DevBuf<float> d;
-  HIPCHK(d.alloc(n));
+  DevArr<float> d;
+  HIPCHK(d.resize(n));
   hipLaunchKernelGGL(k_probe_rand, dim3(1), dim3(1), 0, ctx->stream, seed, packet, n, d.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -4151,7 +4071,7 @@ enum { MULTI_XI = 1, MULTI_ISPEC = 2 };
 struct RedBuf { void* p; size_t n; bool f32; };
 static std::vector<RedBuf> multi_bufs(mcgpu_ctx* c, int what, bool accum) {
   std::vector<RedBuf> v;
-  if (accum && c->d_accum) v.push_back({c->d_accum, c->n_accum, false});
+  if (accum && c->d_accum) v.push_back({c->d_accum, c->d_accum.n, false});
   if ((what & MULTI_XI) && c->d_xI) v.push_back({c->d_xI, xi_dev_values(c), c->xI_bytes == 4});
   if ((what & MULTI_ISPEC) && c->d_I_spec) {   // ray tracing method 2 (radiation_field.f90:91-129)
     v.push_back({c->d_I_spec, (size_t)c->M.n_cells * c->n_phi_I * c->n_theta_I * XI_LINE, false});

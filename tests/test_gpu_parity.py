@@ -1461,3 +1461,27 @@ def test_temperature_and_sed_end_to_end_on_other_grids(grid):
     # (the star's flux spans decades over the wavelengths and, on the Voronoi grid, over the inclinations: absolute floor)
     assert (sc > 0).any() and np.allclose(sg, sc, rtol=0.05, atol=1e-4 * sc.max())
     assert (g["n_sent"][li] >= nch * n2).all()
+
+
+def test_grid_replaced_on_a_live_context():
+    """A context whose cylindrical grid is replaced by a larger one (Engine._upload on the same context) computes what a
+    fresh context on the larger model computes: everything sized per cell -- E_prior above all, which the library once
+    allocated for the first grid only -- follows the grid.  Frozen mode, same seed: counters and packet counts exact,
+    E_abs to the tolerance of the frozen comparisons above."""
+    n = 20000
+    m_small, m_large = M.build_model(M.small()), M.build_model(M.small(n_rad=30, nz=16))
+    assert m_large.n_cells > m_small.n_cells and m_large.n_lambda == m_small.n_lambda
+    prior_small = _oracle(m_small, n).run_thermal(2000, seed=1)["E_abs"]
+    prior_large = _oracle(m_large, n).run_thermal(2000, seed=1)["E_abs"]
+    e = _engine(m_small, n)
+    e.run_thermal(n, seed=7, frozen=True, E_prior=prior_small)
+    e._upload(m_large, float(n))
+    e.model = m_large
+    a = e.run_thermal(n, seed=7, frozen=True, E_prior=prior_large)
+    e.close()
+    f = _engine(m_large, n)
+    b = f.run_thermal(n, seed=7, frozen=True, E_prior=prior_large)
+    f.close()
+    assert a["counters"] == b["counters"], (a["counters"], b["counters"])
+    assert np.array_equal(a["sed"][4], b["sed"][4]) and np.array_equal(a["n_sent"], b["n_sent"])
+    assert np.allclose(a["E_abs"], b["E_abs"], rtol=1e-9, atol=1e-12 * b["E_abs"].max())
