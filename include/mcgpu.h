@@ -201,6 +201,18 @@ int mcgpu_set_midplane_snap(mcgpu_ctx *ctx, int on);
  *                      enough for that to pay (>= 20 crossings per flight, measured by the pass's first launch) and a crossing's
  *                      atomics would touch at least four 64-byte lines (many observers);
  *                      0 = atomics always; 2 = the log always.  Same sums to the order of default-real additions.
+ *                      3 = where a crossing adds at most three default reals to its sub-bin (one to three observers without
+ *                      Stokes tracking, with or without lsepar_contrib; ray-tracing method 1): the deposit itself is a
+ *                      16-byte RECORD {sub-bin | origin, l * weight of every observer}, staged per address-range bucket in
+ *                      LDS, written in 1 KB blocks to a log in HBM and summed per bucket in LDS after every launch -- no
+ *                      sort, no gather, no per-crossing atomics (mc_xirec.hip.h).  Elsewhere 3 runs as 0.  Never chosen
+ *                      by 1.  Where the log cannot be allocated the call runs with atomics.
+ *   "xi_rec_log_mb"   "xi_log" = 3: size of the record log in MiB; 0 (default) = 384 records of 16 bytes per packet of the
+ *                      pass, between 64 MiB and 16 GiB, at most a quarter of the free device memory.  A smaller log
+ *                      means more, shorter launches; a block that finds its part of the log full is added with atomics.
+ *   "xi_rec_buckets"  "xi_log" = 3: staging buckets, 1..96; 0 (default) = what the transport kernel's LDS affords (2 KB each)
+ *   "xi_rec_fold_kb"  "xi_log" = 3: the fold's slice of accumulators in KiB of LDS, 1..144; 0 (default) = 144.  A bucket whose
+ *                      accumulators exceed the slice is folded by several workgroups that each read the whole bucket.
  *   "deposit_log_mb"  size of the binned-deposit log in MiB; 0 (default) = up to 64 GiB (what the packets asked for need), at most a quarter of
  *                      the free device memory.  A smaller log means more, shorter chunks; a
  *                      block that finds its part of the log full is added with atomics.
@@ -236,7 +248,11 @@ int mcgpu_set_option(mcgpu_ctx *ctx, const char *name, int value);
  * "tail_ms", "longest_packet_events" / _crossings / _scatterings / _absorptions / _walks / _steps, and of the last
  * launch's tail: "tail_where" (0: it had none, 1: k_tail finished it, 2: the host threads did), "tail_host_ms",
  * "tail_host_packets", "tail_host_threads", "tail_host_events"; of the last mcgpu_run_mono's commit passes:
- * "xi_log_chunks" (launches that logged their deposits; 0: atomics), "xi_log_records", "xi_log_flights"; of the packed
+ * "xi_log_chunks" (launches that logged their deposits; 0: atomics), "xi_log_records", "xi_log_flights"; with "xi_log" = 3
+ * (all 0 where atomics ran) "xi_rec_chunks" (launches), "xi_rec_records" (deposits made) = "xi_rec_folded" (summed from the
+ * log) + "xi_rec_drained" (left in the staging at the end of a launch: added with atomics) + 64 x "xi_rec_overflow_blocks"
+ * (blocks that found their part of the log full: added with atomics), "xi_rec_buckets", "xi_rec_split" (workgroups that
+ * share a bucket's fold), "xi_rec_fold_ms" (the folds' time), and "xi_rec_log_bytes" (the log this context holds; 0: none); of the packed
  * default-real xI_scatt layout this context's observers get (mcgpu_set_xI_precision): "xi_bin_floats" (default reals per
  * sub-bin), "xi_lines_per_crossing" (64-byte lines one crossing's deposits touch), "xi_split" (1: the split arrangement). */
 int mcgpu_get_info(mcgpu_ctx *ctx, const char *name, double *value);

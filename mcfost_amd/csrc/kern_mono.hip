@@ -19,4 +19,11 @@ const void* kpick_mono(bool l3d, bool pola, bool dark, bool scout, bool f32, boo
     }); }); }); }); });
 }
 
+// the commit pass whose deposits are 16-byte records in the binned log (mc_xirec.hip.h): default-real records, no Stokes tracking
+const void* kpick_mono_rec(bool l3d, bool dark) {
+  return bsel(l3d, [&](auto L3D) { return bsel(dark, [&](auto DARK) -> const void* {
+    return (const void*)k_mono_rec<MCGPU_BV(L3D), MCGPU_BV(DARK)>;
+  }); });
+}
+
 }  // namespace mcgpu

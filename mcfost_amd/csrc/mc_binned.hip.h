@@ -22,6 +22,11 @@
 // flushed WAITS at a wave-uniform point while its wave keeps doing the flushes it owns (bin_settle), so the lowest unflushed block
 // of a bucket is always writable and its flush never waits for anybody: no deadlock.  A block that finds its
 // region of the log full is added to the array with plain atomics (graceful overflow: sizes are a matter of speed).
+//
+// The staging protocol is generic in the record's VALUE type V and in where a record goes when the log does not take it
+// (the SINK).  V = double, sink = the array E: the thermal step's (cell, FP64) records -- bin_lds_bytes, BinStage,
+// bin_carve and every call `bin_xxx(S, A.bin, A.E_abs, ...)` are that instantiation.  A value type that carries its own
+// key (BinKeyed<V>: the SED step's 16-byte XiRec, mc_xirec.hip.h) has no key arrays, neither in LDS nor in the log.
 #pragma once
 #include "mc_device.hip.h"
 
@@ -52,40 +57,56 @@ __device__ inline double bin_energy_scale(const RunArgs& A) {
   return (A.n_folded + started) / A.n_folded;
 }
 
-__host__ __device__ inline size_t bin_lds_bytes(int n_buckets) {
-  return (size_t)n_buckets * (2 * BIN_H * (sizeof(double) + sizeof(unsigned int)) + 6 * sizeof(unsigned int));
+// true: a value of type V holds its record's key (specialised next to the type); the stage and the log keep no key arrays
+template <typename V> struct BinKeyed { static constexpr bool value = false; };
+template <typename V> struct BinSame { typedef V type; };   // (keeps an argument out of template deduction)
+
+template <typename V>
+__host__ __device__ inline size_t bin_lds_bytes_of(int n_buckets) {
+  return (size_t)n_buckets * (2 * BIN_H * (sizeof(V) + (BinKeyed<V>::value ? 0 : sizeof(unsigned int))) + 6 * sizeof(unsigned int));
 }
+__host__ __device__ inline size_t bin_lds_bytes(int n_buckets) { return bin_lds_bytes_of<double>(n_buckets); }
+
+// where a record goes that the log does not take (overflow, end of a launch, the spin's safety valve): the array itself
+__device__ inline void bin_sink_add(double* E, unsigned int key, double v) { atomic_add_f64(&E[key], v); }
 
 // LDS side (one per workgroup)
-struct BinStage {
-  double* vals;         // [n_buckets][2 * BIN_H]
-  unsigned int* keys;   // [n_buckets][2 * BIN_H]
+template <typename V>
+struct BinStageT {
+  V* vals;              // [n_buckets][2 * BIN_H]
+  unsigned int* keys;   // [n_buckets][2 * BIN_H] (BinKeyed<V>: none)
   unsigned int* resv;   // [n_buckets]
   unsigned int* epoch;  // [n_buckets][2]
   unsigned int* done;   // [n_buckets][2]
   unsigned int* wcur;   // [n_buckets] blocks this workgroup has written to its part of the bucket's region
 };
+typedef BinStageT<double> BinStage;
 
-__device__ inline BinStage bin_carve(void* base, int n_buckets) {
-  BinStage S;
-  S.vals = reinterpret_cast<double*>(base);
+// (base: aligned like V)
+template <typename V>
+__device__ inline BinStageT<V> bin_carve_of(void* base, int n_buckets) {
+  BinStageT<V> S;
+  S.vals = reinterpret_cast<V*>(base);
   S.keys = reinterpret_cast<unsigned int*>(S.vals + (size_t)n_buckets * 2 * BIN_H);
-  S.epoch = S.keys + (size_t)n_buckets * 2 * BIN_H;  // (8-byte aligned: both halves' epochs are read as one word)
+  S.epoch = S.keys + (BinKeyed<V>::value ? (size_t)0 : (size_t)n_buckets * 2 * BIN_H);  // (8-byte aligned: both halves' epochs are read as one word)
   S.done = S.epoch + 2 * n_buckets;
   S.resv = S.done + 2 * n_buckets;
   S.wcur = S.resv + n_buckets;
   return S;
 }
+__device__ inline BinStage bin_carve(void* base, int n_buckets) { return bin_carve_of<double>(base, n_buckets); }
 
 // (every thread of the workgroup, before a __syncthreads())
-__device__ inline void bin_init(const BinStage& S, int n_buckets) {
+template <typename V>
+__device__ inline void bin_init(const BinStageT<V>& S, int n_buckets) {
   for (int i = threadIdx.x; i < 6 * n_buckets; i += blockDim.x) S.epoch[i] = 0u;
 }
 
 __device__ inline unsigned int bin_ldu(const unsigned int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 // the whole wave writes block (b, h) to the log and opens the half for the next epoch
-__device__ inline void bin_flush_block(const BinStage& S, const BinLog& L, double* E, int b, int h, int lane) {
+template <typename V, typename LOG, typename SINK>
+__device__ inline void bin_flush_block(const BinStageT<V>& S, const LOG& L, SINK E, int b, int h, int lane) {
   unsigned int blk = 0u;
   if (lane == 0) blk = atomicAdd(&S.wcur[b], 1u);
   blk = __shfl(blk, 0);
@@ -93,14 +114,15 @@ __device__ inline void bin_flush_block(const BinStage& S, const BinLog& L, doubl
   const bool fits = blk < cap;
   for (int l = lane; l < BIN_H; l += BIN_WAVE) {
     const int slot = (b * 2 + h) * BIN_H + l;
-    const unsigned int key = S.keys[slot];
-    const double v = S.vals[slot];
+    unsigned int key = 0u;
+    if constexpr (!BinKeyed<V>::value) key = S.keys[slot];
+    const V v = S.vals[slot];
     if (fits) {
       const size_t at = ((size_t)L.off[b] + (size_t)cap * blockIdx.x + blk) * BIN_H + l;
-      L.keys[at] = key;
+      if constexpr (!BinKeyed<V>::value) L.keys[at] = key;
       L.vals[at] = v;
     } else {
-      atomic_add_f64(&E[key], v);
+      bin_sink_add(E, key, v);
     }
   }
   __threadfence_block();  // the slots have been read before the half opens again
@@ -124,7 +146,8 @@ struct BinLane {
 __device__ inline void bin_lane_init(BinLane& P) { P.seen = 0u; P.b = 0; P.h = 0; P.open = false; }
 
 // the flushes this wave owes: blocks whose last record one of its lanes wrote (converged control flow)
-__device__ inline void bin_settle(const BinStage& S, const BinLog& L, double* E, int lane, BinLane& P) {
+template <typename V, typename LOG, typename SINK>
+__device__ inline void bin_settle(const BinStageT<V>& S, const LOG& L, SINK E, int lane, BinLane& P) {
   unsigned long long m = __ballot(P.open && P.seen + 1u == (unsigned int)BIN_H);
   P.open = false;
   while (m) {
@@ -135,10 +158,12 @@ __device__ inline void bin_settle(const BinStage& S, const BinLog& L, double* E,
   }
 }
 
-// One deposit per lane with `active` (cell ic, 0-based; value v).  MUST be called by every lane of the wave in
+// One deposit per lane with `active` (cell ic, 0-based -- the index the bucket is taken from --; value v).  MUST be called by every lane of the wave in
 // converged control flow; bin_settle(P) must follow the last call of a loop before the wave does anything that other
 // waves may wait for.
-__device__ inline void bin_deposit(const BinStage& S, const BinLog& L, double* E, int lane, BinLane& P, bool active, int ic, double v) {
+template <typename V, typename LOG, typename SINK>
+__device__ inline void bin_deposit(const BinStageT<V>& S, const LOG& L, SINK E, int lane, BinLane& P, bool active, int ic,
+                                   typename BinSame<V>::type v) {
   const int b = active ? (ic >> L.shift) : 0;
   unsigned int pos = 0u;
   unsigned long long ep2 = 0ull;
@@ -158,7 +183,7 @@ __device__ inline void bin_deposit(const BinStage& S, const BinLog& L, double* E
   for (int spin = 0;; ++spin) {
     if (pend && ep == e) {
       const int slot = (b * 2 + h) * BIN_H + (int)(pos % BIN_H);
-      S.keys[slot] = (unsigned int)ic;
+      if constexpr (!BinKeyed<V>::value) S.keys[slot] = (unsigned int)ic;
       S.vals[slot] = v;
       __threadfence_block();  // the record is in place before it is counted
       P.seen = atomicAdd(&S.done[b * 2 + h], 1u);
@@ -170,21 +195,24 @@ __device__ inline void bin_deposit(const BinStage& S, const BinLog& L, double* E
     bin_settle(S, L, E, lane, P);
     __builtin_amdgcn_s_sleep(1);
     if (pend) ep = bin_ldu(&S.epoch[b * 2 + h]);
-    if (spin > (1 << 22)) { if (pend) atomic_add_f64(&E[ic], v); pend = false; }  // (never: a logic error must not hang the GPU)
+    if (spin > (1 << 22)) { if (pend) bin_sink_add(E, (unsigned int)ic, v); pend = false; }  // (never: a logic error must not hang the GPU)
   }
 }
 
 // End of a launch (after a __syncthreads() behind the last deposit): what is left in the half-buffers goes to the
 // array directly -- at most 63 records per bucket and workgroup -- and the workgroup publishes how many blocks it
 // wrote to its parts of the log.
-__device__ inline void bin_drain(const BinStage& S, const BinLog& L, double* E) {
+template <typename V, typename LOG, typename SINK>
+__device__ inline void bin_drain(const BinStageT<V>& S, const LOG& L, SINK E) {
   for (int b = 0; b < L.n_buckets; ++b) {
     const unsigned int r = S.resv[b];
     const unsigned int k = r / BIN_H, n = r % BIN_H;
     const int h = (int)(k & 1u);
     for (unsigned int l = threadIdx.x; l < n; l += blockDim.x) {
       const int slot = (b * 2 + h) * BIN_H + (int)l;
-      atomic_add_f64(&E[S.keys[slot]], S.vals[slot]);
+      unsigned int key = 0u;
+      if constexpr (!BinKeyed<V>::value) key = S.keys[slot];
+      bin_sink_add(E, key, S.vals[slot]);
     }
     if (threadIdx.x == 0 && n) atomicAdd(&L.stats[1], (unsigned long long)n);
   }

@@ -25,6 +25,7 @@
 #pragma once
 #include "mc_device.hip.h"
 #include "mc_xi32.hip.h"
+#include "mc_xirec.hip.h"
 
 namespace mcgpu {
 
@@ -74,6 +75,8 @@ struct MonoArgs {
   unsigned long long item_lo;           // COMMIT: the launch runs the work items [item_lo, item_lo + n_items)
   int kf_lds;                           // COMMIT: kappa_factor(1:n_cells) is staged in the workgroup's LDS (mono_lds_bytes)
   int rowf;                             // COMMIT: > 0: the per-lane results are weight rows of this many default reals
+  // the commit pass's deposits as 16-byte records in a binned log (k_mono_rec; mc_xirec.hip.h)
+  XiRecLog rec;
 };
 
 // per-lane results of angles_scatt_rt1, kept in LDS as [q][thread]
@@ -118,6 +121,11 @@ __host__ __device__ inline size_t mono_lds_bytes(const DevModel& M, int nRT, int
   return b;
 }
 
+// k_mono_rec: the staging buckets (mc_binned.hip.h, 16-byte records) start behind the lean kernel's LDS
+__host__ __device__ inline size_t xirec_stage_at(const DevModel& M, int nRT, int threads, bool pola) {
+  return (mono_lds_bytes(M, nRT, threads, pola, true, true) + 15) / 16 * 16;
+}
+
 // angles_scatt_rt1 (dust_ray_tracing.f90:409-476) for this lane's direction
 // w_mu != nullptr (the commit pass with default-real records and one dust class): the flight's DEPOSIT WEIGHTS are stored
 // instead of the angles -- between two interactions the packet's Stokes vector, its direction and hence the product
@@ -137,11 +145,10 @@ __device__ __forceinline__ void row_put(float* rowimg, int p, int slot, float v)
   ((lds_f32_t*)rowimg)[(((size_t)(p >> 2) * blockDim.x + slot) << 2) + (p & 3)] = v;
 }
 #endif
-template <bool POLA>
-__device__ inline void angles_scatt_rt1_one(const DevModel& M, const MonoArgs& A, const RtScratch& R, int q, int slot, double u,
-                                             double v, double w, const float* w_mu, const double* S, float* row,
-                                             float* rowimg = nullptr, bool star = false) {
-  const double ur = A.rt_u[q], vr = A.rt_v[q], wr = A.rt_w[q % A.RT_n_incl];
+// the scattering-angle bin k of a flight (u, v, w) towards observer q (:430-434); wr: the observer's w
+__device__ __forceinline__ int rt1_angle_bin(const DevModel& M, const MonoArgs& A, int q, double u, double v, double w, double& wr) {
+  const double ur = A.rt_u[q], vr = A.rt_v[q];
+  wr = A.rt_w[q % A.RT_n_incl];
   const float cos_scatt = (float)nd_add(nd_add(nd_mul(ur, u), nd_mul(vr, v)), nd_mul(wr, w));
   // k = nint(acos(cos_scatt) * nang / pi) in default real (:430-434).  The default-real arccosine of the runtime decides
   // the bin unless the quotient lies within delta = 1.2e-6 nang of a bin edge (2.2e-4 at 180 bins) -- the roundings of
@@ -160,6 +167,15 @@ __device__ inline void angles_scatt_rt1_one(const DevModel& M, const MonoArgs& A
   }
   if (k > M.nang) k = M.nang;
   if (k < 1) k = 1;
+  return k;
+}
+
+template <bool POLA>
+__device__ inline void angles_scatt_rt1_one(const DevModel& M, const MonoArgs& A, const RtScratch& R, int q, int slot, double u,
+                                             double v, double w, const float* w_mu, const double* S, float* row,
+                                             float* rowimg = nullptr, bool star = false) {
+  double wr;
+  const int k = rt1_angle_bin(M, A, q, u, v, w, wr);
   if (!row && !rowimg) R.itheta[q * blockDim.x + slot] = k;
 #ifndef MCGPU_LANE_EMULATION   // (the lane emulation has no default-real commit pass)
   if (!POLA && w_mu) {
@@ -948,12 +964,15 @@ __device__ inline void xlog_append(const MonoArgs& A, XiLogCursor& C, bool on, u
 // SCOUT: no deposits, no SED; records hits.  Otherwise the COMMIT pass.
 // SPH: the grid operators of spherical_grid.f90 (as thermal_body has them)
 // LOG (with F32, one dust class): the deposits go to the log instead of xI_scatt (see "The deposits as a log")
-template <bool L3D, bool POLA, bool DARK, bool SCOUT, bool F32 = false, bool SPH = false, bool LOG = false>
+// REC (with F32, one dust class, no Stokes tracking, <= 3 observers): a deposit is a 16-byte record {sub-bin, l * w[q]}
+// handed to the staging of mc_binned.hip.h (mc_xirec.hip.h); the lane keeps its flight's weights itself, so the kernel
+// has LOG's LDS -- no per-lane results, no tiles -- plus the staging buckets behind it
+template <bool L3D, bool POLA, bool DARK, bool SCOUT, bool F32 = false, bool SPH = false, bool LOG = false, bool REC = false>
 __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, double* lds_base) {
   const Lds T = lds_carve(lds_base, M, true);
   lds_stage_mono(T, M, A.p_lambda);
   const int na1 = M.nang + 1;
-  const MonoLds ML = mono_lds_setup<POLA>(M, A, lds_base, true, LOG || SCOUT);   // (a scout pass makes no deposits: no per-lane results, no tiles)
+  const MonoLds ML = mono_lds_setup<POLA>(M, A, lds_base, true, LOG || SCOUT || REC);   // (a scout pass makes no deposits: no per-lane results, no tiles)
   const float* mu = ML.mu;
   const RtScratch& R = ML.R;
   double* const tile = ML.tile;
@@ -983,6 +1002,18 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
   XiLogCursor LC = {0ull, 0ull, 0ull, 0ull};
   unsigned int my_fid = 0u;
   const size_t row_floats = (size_t)A.nRT * (POLA ? 4 : 1);
+  // REC: the staging buckets behind the kernel's own LDS, the flight's <= 3 deposit weights, the records made
+  const BinStageT<XiRec> RS = bin_carve_of<XiRec>(reinterpret_cast<char*>(lds_base) + xirec_stage_at(M, A.nRT, (int)blockDim.x, POLA),
+                                                  REC ? A.rec.n_buckets : 0);
+  const XiRecSink RK = {reinterpret_cast<float*>(A.xI), A.xi, A.nRT, (unsigned int)((size_t)M.n_cells * A.n_theta_rt * A.n_az_rt)};
+  BinLane RP;
+  bin_lane_init(RP);
+  float rec_w0 = 0.0f, rec_w1 = 0.0f, rec_w2 = 0.0f;
+  unsigned int c_rec = 0u;
+  if (REC) {
+    bin_init(RS, A.rec.n_buckets);
+    __syncthreads();
+  }
 #endif
 
   for (;;) {
@@ -1082,7 +1113,7 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
 #endif
 #ifndef MCGPU_LANE_EMULATION
     // (the commit pass with default-real records and one dust class: the new flights' observer weights by the whole wave)
-    constexpr bool kAnglesByWave = F32 && !SCOUT && !LOG;
+    constexpr bool kAnglesByWave = F32 && !SCOUT && !LOG && !REC;   // (LOG and REC keep no per-lane results and no tiles in LDS)
     if (kAnglesByWave && A.rt1 && !var) angles_scatt_rt1_wave<POLA>(M, A, R, st == S_NEWFLIGHT, u, v, w, mu, S, tile, ML.row, flag_star);
 #else
     constexpr bool kAnglesByWave = false;
@@ -1097,6 +1128,13 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
       if (LOG && !SCOUT && A.rt1) {   // the flight's deposit weights -> its row of the log
         my_fid = (unsigned int)fid_new;
         angles_scatt_rt1<POLA>(M, A, R, u, v, w, mu, S, A.log_rows + (fid_new < A.rows_cap ? fid_new : 0ull) * row_floats);
+      } else if (REC && !SCOUT && A.rt1) {   // the flight's deposit weights stay with the lane (angles_scatt_rt1_one's wI)
+#pragma unroll 1
+        for (int q = 0; q < A.nRT; ++q) {
+          double wr;
+          const float wI = (float)(S[0] * (double)mu[rt1_angle_bin(M, A, q, u, v, w, wr)]);
+          if (q == 0) rec_w0 = wI; else if (q == 1) rec_w1 = wI; else rec_w2 = wI;
+        }
       } else
 #endif
       if (!SCOUT && A.rt1 && !(kAnglesByWave && !var))
@@ -1211,6 +1249,15 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
         if constexpr (LOG) {
           const unsigned int bin = (unsigned int)((((size_t)(dep.icell - 1) * A.n_theta_rt + (dep.psup - 1)) * A.n_az_rt) + (dep.phik - 1));
           xlog_append(A, LC, dep.on, bin | (flag_star ? 0x80000000u : 0u), my_fid, (float)dep.l, lane);
+        } else if constexpr (REC) {
+          const bool on = dep.on && !MCGPU_DIAG(A.flags, 1);
+          const unsigned int bin = (unsigned int)((((size_t)(dep.icell - 1) * A.n_theta_rt + (dep.psup - 1)) * A.n_az_rt) + (dep.phik - 1));
+          const float lf = (float)dep.l;
+          XiRec r;
+          r.key = bin | (flag_star ? 0x80000000u : 0u);
+          r.v[0] = lf * rec_w0; r.v[1] = lf * rec_w1; r.v[2] = lf * rec_w2;
+          if (on) c_rec++;
+          bin_deposit<XiRec>(RS, A.rec, RK, lane, RP, on, (int)bin, r);
         } else if constexpr (F32) {
           if (ML.row) deposit_rt1_wave_row(A, ML.row, dep, flag_star, tile, tile_addr);
           else deposit_rt1_wave_f32<POLA>(M, A, R, mu, dep, S, flag_star, tile, tile_addr, tile_mask);
@@ -1219,9 +1266,20 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
         deposit_rt1_wave<POLA>(M, A, R, mu, dep, S, flag_star, tile, tile_addr, tile_mask);
       }
     }
+#ifndef MCGPU_LANE_EMULATION
+    if (REC) bin_settle(RS, A.rec, RK, lane, RP);   // (wave-uniform: the flushes this wave owes, before it turns to emission and interactions)
+#endif
   }
 #ifndef MCGPU_LANE_EMULATION
   if (LOG && !SCOUT) xlog_pad(A, LC.rec_next, LC.rec_end, lane);   // (what the wave reserved and did not use sorts behind the records)
+  if (REC) {   // the end of the launch: what the half-buffers still hold goes to xI_scatt, the block counts to the fold
+    bin_settle(RS, A.rec, RK, lane, RP);
+    __syncthreads();
+    bin_drain(RS, A.rec, RK);
+    unsigned long long n_rec = c_rec;
+    for (int off = 32; off > 0; off >>= 1) n_rec += __shfl_down(n_rec, off);
+    if (lane == 0 && n_rec) atomicAdd(&A.rec.stats[3], n_rec);
+  }
 #endif
 
   if (!SCOUT) {
@@ -1243,6 +1301,16 @@ __global__ void __launch_bounds__(512) k_mono(const DevModel M, const MonoArgs A
   extern __shared__ double lds_raw[];
   mono_body<L3D, POLA, DARK, SCOUT, F32, false, LOG>(M, A, lds_raw);
 }
+
+#ifndef MCGPU_LANE_EMULATION
+// ... whose deposits are 16-byte records in the binned log (mono_body's REC; default-real records, no Stokes tracking).
+// A kernel of its own name rather than one more flag of k_mono: the existing instantiations keep their symbols.
+template <bool L3D, bool DARK>
+__global__ void __launch_bounds__(512) k_mono_rec(const DevModel M, const MonoArgs A) {
+  extern __shared__ __attribute__((aligned(16))) double lds_raw_rec[];   // (the staged records are written 16 bytes at a time)
+  mono_body<L3D, false, DARK, false, true, false, false, true>(M, A, lds_raw_rec);
+}
+#endif
 
 // ... on a spherical grid (no dark zone there)
 template <bool L3D, bool POLA, bool SCOUT, bool F32 = false>

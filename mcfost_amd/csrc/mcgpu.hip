@@ -232,6 +232,23 @@ struct mcgpu_ctx {
   DevArr<char> d_xlog_temp;
   int xlog_chunks = 0;              // launches of the last wavelength's commit passes
   unsigned long long xlog_records = 0, xlog_flights = 0;   // ... and what they logged
+  // ... or as 16-byte records in a binned log ("xi_log" = 3; mc_xirec.hip.h): the log's arrays, the view the kernels take, its plan
+  int opt_xi_rec_log_mb = 0;        // size of the log in MiB (0: a share of the free device memory)
+  int opt_xi_rec_buckets = 0;       // staging buckets (0: what the transport kernel's LDS affords, at most BIN_MAX_BUCKETS)
+  int opt_xi_rec_fold_kb = 0;       // the fold's slice of accumulators in KiB (0: what the LDS of a CU allows)
+  DevArr<XiRec> d_xrec_log;
+  DevArr<unsigned int> d_xrec_count, d_xrec_off, d_xrec_cap;
+  DevArr<unsigned long long> d_xrec_stats;
+  DevArr<double> d_xrec_want;       // [n_buckets] scratch of k_plan_bins
+  XiRecLog xrec{};
+  unsigned long long xrec_total_blocks = 0;
+  bool xrec_log_capped = false;     // the log was cut to a share of the free memory
+  int xrec_max_parts = 0;
+  // the last mcgpu_run_mono (all 0 where atomics ran)
+  int xrec_chunks = 0, xrec_buckets = 0, xrec_split = 0;
+  unsigned long long xrec_records = 0, xrec_folded = 0, xrec_overflow = 0, xrec_drained = 0;
+  double xrec_fold_ms = 0.0;        // ... and the time of its folds
+  OwnedEvent ev_xrec0, ev_xrec1;    // around a fold
   // Voronoi grid (mc_voronoi.hip.h)
   bool voro = false;
   VoroGrid V;
@@ -569,11 +586,35 @@ static void bin_release(mcgpu_ctx* ctx) {
   ctx->bin_max_parts = 0;
 }
 
+constexpr int XI_REC_FOLD_KB_MAX = 144;   // the fold's slice: the LDS of a CU (160 KiB) less some room for the runtime's own
+
+// the record log of the SED commit pass ("xi_log" = 3): allocated by the first commit pass that uses it, kept until the
+// option that selects or sizes it changes
+static void xi_rec_release(mcgpu_ctx* ctx) {
+  ctx->d_xrec_log.reset(); ctx->d_xrec_count.reset(); ctx->d_xrec_off.reset(); ctx->d_xrec_cap.reset();
+  ctx->d_xrec_stats.reset(); ctx->d_xrec_want.reset();
+  ctx->xrec = XiRecLog{};
+  ctx->xrec_total_blocks = 0;
+  ctx->xrec_max_parts = 0;
+  ctx->xrec_log_capped = false;
+}
+
 extern "C" int mcgpu_set_option(mcgpu_ctx* ctx, const char* name, int value) {
   if (!ctx || !name) return MCGPU_ERR_ARG;
   if (!strcmp(name, "deposit")) { if (value < 0 || value > 3) return fail(ctx, MCGPU_ERR_ARG, "deposit: 0, 1, 2 or 3"); ctx->opt_deposit = value; }
   else if (!strcmp(name, "tail")) { if (value < -1 || value > (1 << 20)) return fail(ctx, MCGPU_ERR_ARG, "tail: -1 (automatic), 0 (off), or the packets left per workgroup at the hand-over"); ctx->opt_tail = value; }
-  else if (!strcmp(name, "xi_log")) { if (value < 0 || value > 2) return fail(ctx, MCGPU_ERR_ARG, "xi_log: 0, 1 or 2"); ctx->opt_xi_log = value; }
+  else if (!strcmp(name, "xi_log")) {
+    if (value < 0 || value > 3) return fail(ctx, MCGPU_ERR_ARG, "xi_log: 0, 1, 2 or 3");
+    if (value != 3 && ctx->d_xrec_log) { hipSetDevice(ctx->device); xi_rec_release(ctx); }
+    ctx->opt_xi_log = value;
+  }
+  else if (!strcmp(name, "xi_rec_log_mb")) {
+    if (value < 0) return fail(ctx, MCGPU_ERR_ARG, "xi_rec_log_mb: >= 0 (0: automatic)");
+    if (value != ctx->opt_xi_rec_log_mb && ctx->d_xrec_log) { hipSetDevice(ctx->device); xi_rec_release(ctx); }
+    ctx->opt_xi_rec_log_mb = value;
+  }
+  else if (!strcmp(name, "xi_rec_buckets")) { if (value < 0 || value > BIN_MAX_BUCKETS) return fail(ctx, MCGPU_ERR_ARG, "xi_rec_buckets: 0 (automatic) .. 96"); ctx->opt_xi_rec_buckets = value; }
+  else if (!strcmp(name, "xi_rec_fold_kb")) { if (value < 0 || value > XI_REC_FOLD_KB_MAX) return fail(ctx, MCGPU_ERR_ARG, "xi_rec_fold_kb: 0 (automatic) .. 144"); ctx->opt_xi_rec_fold_kb = value; }
   else if (!strcmp(name, "tail_where")) { if (value < 0 || value > 2) return fail(ctx, MCGPU_ERR_ARG, "tail_where: 0 (automatic), 1 (device), 2 (host)"); ctx->opt_tail_where = value; }
   else if (!strcmp(name, "host_threads")) { if (value < 0 || value > 256) return fail(ctx, MCGPU_ERR_ARG, "host_threads: 0 (automatic) .. 256"); ctx->opt_host_threads = value; }
   else if (!strcmp(name, "tail_host_packets")) { if (value < 0 || value > 65536) return fail(ctx, MCGPU_ERR_ARG, "tail_host_packets: 0 (automatic) .. 65536"); ctx->opt_tail_host_max = value; }
@@ -658,6 +699,17 @@ extern "C" int mcgpu_get_info(mcgpu_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "xi_log_chunks")) *value = ctx->xlog_chunks;     // the last mcgpu_run_mono: launches of its commit passes,
   else if (!strcmp(name, "xi_log_records")) *value = (double)ctx->xlog_records;   // records (crossings with a deposit) and
   else if (!strcmp(name, "xi_log_flights")) *value = (double)ctx->xlog_flights;   // flights they logged (0: atomics)
+  // ... or as records in the binned log ("xi_log" = 3): launches, records made = records the folds summed + records added at
+  // the end of a launch + 64 x blocks that found their part of the log full; the buckets, the fold's split, the log's size
+  else if (!strcmp(name, "xi_rec_chunks")) *value = ctx->xrec_chunks;
+  else if (!strcmp(name, "xi_rec_records")) *value = (double)ctx->xrec_records;
+  else if (!strcmp(name, "xi_rec_folded")) *value = (double)ctx->xrec_folded;
+  else if (!strcmp(name, "xi_rec_overflow_blocks")) *value = (double)ctx->xrec_overflow;
+  else if (!strcmp(name, "xi_rec_drained")) *value = (double)ctx->xrec_drained;
+  else if (!strcmp(name, "xi_rec_buckets")) *value = ctx->xrec_buckets;
+  else if (!strcmp(name, "xi_rec_split")) *value = ctx->xrec_split;
+  else if (!strcmp(name, "xi_rec_fold_ms")) *value = ctx->xrec_fold_ms;
+  else if (!strcmp(name, "xi_rec_log_bytes")) *value = ctx->d_xrec_log ? (double)ctx->xrec_total_blocks * (double)(XIREC_H * sizeof(XiRec)) : 0.0;
   else if (!strcmp(name, "tau_midplane")) *value = ctx->tau_midplane;
   // the packed default-real layout of xI_scatt this context would use (mc_xi32.hip.h; needs mcgpu_set_rt1): default reals
   // per sub-bin, 64-byte lines one crossing's deposits touch, 1 = the split arrangement
@@ -2607,7 +2659,7 @@ extern "C" int mcgpu_rt2_source(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, int p_la
 // 3 observers 207 ms with atomics against 333 with the log, 6 observers 296 against 349, 10 observers 384 against 367).
 static bool xi_log_applicable(const mcgpu_ctx* ctx, bool rt1) {
   const DevModel& M = ctx->M;
-  if (!(rt1 && ctx->opt_xi_log != 0 && ctx->xI_bytes == 4 && !M.n_classes && !ctx->voro && !M.grid_sph)) return false;
+  if (!(rt1 && ctx->opt_xi_log != 0 && ctx->opt_xi_log != 3 && ctx->xI_bytes == 4 && !M.n_classes && !ctx->voro && !M.grid_sph)) return false;
   return ctx->opt_xi_log == 2 || xi32_lines_touched(xi_layout_of(ctx), ctx->RT_n_incl * ctx->RT_n_az) >= 4;
 }
 
@@ -2643,6 +2695,175 @@ static int xi_log_prepare(mcgpu_ctx* ctx, unsigned long long n_items, int nRT, b
   return MCGPU_OK;
 }
 
+// ---- the commit pass with its deposits as 16-byte records in a binned log (option "xi_log" = 3; mc_xirec.hip.h) ----------
+// Where the path applies: default-real records, one dust class, a cylindrical grid, at most three values per deposit.
+// Elsewhere a context with "xi_log" = 3 runs as with 0.
+static bool xi_rec_applicable(const mcgpu_ctx* ctx, bool rt1) {
+  const DevModel& M = ctx->M;
+  if (!(rt1 && ctx->opt_xi_log == 3 && ctx->xI_bytes == 4 && !M.n_classes && !ctx->voro && !M.grid_sph)) return false;
+  if ((unsigned long long)M.n_cells * ctx->n_theta_rt * ctx->n_az_rt >= 0x80000000ull) return false;   // (bit 31 of the key is flag_star)
+  return xirec_applies(ctx->RT_n_incl * ctx->RT_n_az, ctx->lsepar_pola != 0, ctx->lsepar_contrib != 0);
+}
+
+// The launch geometry of k_mono_rec and of its fold.  Two budgets meet here.  A staging bucket costs the transport
+// kernel 2 KB of LDS per workgroup, next to the commit pass's tables: the bucket count is what three workgroups of 256
+// threads per CU can afford (the occupancy of the kernel that logs to the sorted log), two or one where that leaves
+// fewer than 16 buckets, at most BIN_MAX_BUCKETS.  A bucket's accumulators (xirec_slots default reals per sub-bin) may
+// then be larger than one fold slice: `split` workgroups share the bucket, each reads the whole region and keeps its own
+// sub-range -- the fold reads split x 16 bytes per record.
+struct XiRecGeom {
+  const void* fn;
+  int threads, n_buckets, shift, split, slice_sub;
+  size_t lds, fold_lds;
+};
+static bool xi_rec_geometry(const mcgpu_ctx* ctx, int nRT, int block_threads, XiRecGeom& G) {
+  const DevModel& M = ctx->M;
+  G.fn = kpick_mono_rec(M.l3D != 0, M.dark != nullptr);
+  G.threads = (block_threads > 0 && block_threads <= 512 && block_threads % 64 == 0) ? block_threads : 256;
+  const size_t base = xirec_stage_at(M, nRT, G.threads, false), per_bucket = bin_lds_bytes_of<XiRec>(1);
+  const size_t lds_cap = 160 * 1024 - 512;
+  size_t nb_fit = 0;
+  for (int per_cu = 768 / G.threads > 0 ? 768 / G.threads : 1; per_cu >= 1; --per_cu) {
+    nb_fit = lds_cap / per_cu > base ? (lds_cap / per_cu - base) / per_bucket : 0;
+    if (nb_fit >= (size_t)(per_cu > 1 ? 16 : 1)) break;
+  }
+  if (nb_fit < 1) return false;
+  size_t nb_max = nb_fit < (size_t)BIN_MAX_BUCKETS ? nb_fit : (size_t)BIN_MAX_BUCKETS;
+  if (ctx->opt_xi_rec_buckets > 0 && (size_t)ctx->opt_xi_rec_buckets < nb_max) nb_max = (size_t)ctx->opt_xi_rec_buckets;
+  const unsigned long long n_sub = (unsigned long long)M.n_cells * ctx->n_theta_rt * ctx->n_az_rt;
+  G.shift = 0;
+  while (((n_sub + (1ull << G.shift) - 1) >> G.shift) > nb_max) ++G.shift;
+  G.n_buckets = (int)((n_sub + (1ull << G.shift) - 1) >> G.shift);
+  G.lds = base + bin_lds_bytes_of<XiRec>(G.n_buckets);
+  const int slots = xirec_slots(xi_layout_of(ctx), nRT);
+  const size_t fold_bytes = (size_t)(ctx->opt_xi_rec_fold_kb > 0 ? ctx->opt_xi_rec_fold_kb : XI_REC_FOLD_KB_MAX) * 1024;
+  unsigned long long slice = fold_bytes / (sizeof(float) * slots);
+  if (slice > (1ull << G.shift)) slice = 1ull << G.shift;
+  G.slice_sub = (int)slice;
+  G.split = (int)(((1ull << G.shift) + slice - 1) / slice);
+  G.fold_lds = (size_t)G.slice_sub * slots * sizeof(float);
+  return true;
+}
+
+// The log for this geometry.  Automatic size: 256 records of 16 bytes per packet of the pass with half as much again,
+// between 64 MiB and 16 GiB and at most a quarter of the device's free memory; an existing log is kept while it is large
+// enough.  false: the log could not be had (the caller deposits with atomics; nothing is left allocated).
+static bool xi_rec_prepare(mcgpu_ctx* ctx, const XiRecGeom& G, int n_parts, unsigned long long n_items) {
+  const size_t block_bytes = (size_t)XIREC_H * sizeof(XiRec);
+  double want_b = (double)n_items * 256.0 * 1.5 * (double)sizeof(XiRec);
+  if (want_b < 64.0 * 1048576.0) want_b = 64.0 * 1048576.0;
+  if (want_b > 16.0 * 1073741824.0) want_b = 16.0 * 1073741824.0;
+  if (ctx->opt_xi_rec_log_mb > 0) want_b = (double)((size_t)ctx->opt_xi_rec_log_mb << 20);
+  const bool same = ctx->d_xrec_log && ctx->xrec.n_buckets == G.n_buckets && ctx->xrec.shift == G.shift && ctx->xrec_max_parts >= n_parts;
+  if (same && (ctx->opt_xi_rec_log_mb > 0 || (double)ctx->xrec_total_blocks * (double)block_bytes >= 0.999 * want_b || ctx->xrec_log_capped))
+    return true;
+  xi_rec_release(ctx);
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+  size_t bytes = (size_t)want_b;
+  if (ctx->opt_xi_rec_log_mb <= 0 && bytes > free_b / 4) { bytes = free_b / 4; ctx->xrec_log_capped = true; }
+  unsigned long long blocks = bytes / block_bytes;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 0xFFFFFFFFull) blocks = 0xFFFFFFFFull;  // (block indices are 32-bit)
+  const size_t nb = (size_t)G.n_buckets;
+  if (ctx->d_xrec_log.resize(blocks * XIREC_H) != hipSuccess || ctx->d_xrec_count.resize(nb * n_parts) != hipSuccess ||
+      ctx->d_xrec_stats.resize(4) != hipSuccess || ctx->d_xrec_off.resize(nb) != hipSuccess || ctx->d_xrec_cap.resize(nb) != hipSuccess ||
+      ctx->d_xrec_want.resize(nb) != hipSuccess ||
+      hipMemsetAsync(ctx->d_xrec_count, 0, nb * n_parts * sizeof(unsigned int), ctx->stream) != hipSuccess) {
+    xi_rec_release(ctx);
+    (void)hipGetLastError();   // (the failed allocation is not this call's error: it runs with atomics)
+    return false;
+  }
+  ctx->xrec.vals = ctx->d_xrec_log; ctx->xrec.keys = nullptr; ctx->xrec.count = ctx->d_xrec_count; ctx->xrec.stats = ctx->d_xrec_stats;
+  ctx->xrec.off = ctx->d_xrec_off; ctx->xrec.cap = ctx->d_xrec_cap;
+  ctx->xrec.n_buckets = G.n_buckets; ctx->xrec.shift = G.shift; ctx->xrec.n_parts = n_parts;
+  ctx->xrec_total_blocks = blocks;
+  ctx->xrec_max_parts = n_parts;
+  return true;
+}
+
+// One commit pass with its deposits as records, in commit_mono's scheme: a short first launch with uniform regions
+// (k_plan_uniform) measures the records per packet and per bucket, k_plan_bins plans every following launch -- sized for
+// what 60 % of the log holds at that rate, the regions carry half as much again --, and every launch is followed by its
+// fold.  A region that is too small anyway costs atomics, not the result (graceful overflow).  Where the staging does
+// not fit or the log cannot be allocated the pass (and the rest of the call: *mode = 0) runs with atomics.
+static int commit_mono_rec(mcgpu_ctx* ctx, MonoArgs A, int grid_blocks, int block_threads, int* mode) {
+  const DevModel& M = ctx->M;
+  const unsigned long long n_total = A.n_items;
+  XiRecGeom G;
+  bool ok = xi_rec_geometry(ctx, A.nRT, block_threads, G);
+  int blocks_full = grid_blocks;
+  if (ok) {
+    HIPCHK(hipFuncSetAttribute(G.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.lds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_fold_xirec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.fold_lds));
+    if (blocks_full <= 0) {
+      int occ = 1;
+      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, G.fn, G.threads, G.lds));
+      blocks_full = ctx->prop.multiProcessorCount * (occ < 1 ? 1 : occ);
+    }
+    ok = xi_rec_prepare(ctx, G, blocks_full, n_total);
+  }
+  if (!ok) {
+    *mode = 0;
+    return launch_mono<false>(ctx, A, grid_blocks, block_threads);
+  }
+  if (!ctx->ev_xrec0.h) HIPCHK(hipEventCreate(&ctx->ev_xrec0.h));
+  if (!ctx->ev_xrec1.h) HIPCHK(hipEventCreate(&ctx->ev_xrec1.h));
+  const unsigned int n_sub = (unsigned int)((size_t)M.n_cells * A.n_theta_rt * A.n_az_rt);
+  ctx->xrec_buckets = G.n_buckets; ctx->xrec_split = G.split;
+  A.rec = ctx->xrec;
+  A.kf_lds = 0; A.rowf = 0;
+  const double log_records = (double)ctx->xrec_total_blocks * XIREC_H;
+  unsigned long long done = 0, chunk = 16384ull, last_chunk = 0;
+  int last_parts = 0;
+  while (done < n_total) {
+    unsigned long long c = chunk < n_total - done ? chunk : n_total - done;
+    int blocks = blocks_full;
+    const unsigned long long need = (c + G.threads - 1) / G.threads;
+    if (grid_blocks <= 0 && (unsigned long long)blocks > need) blocks = (int)(need ? need : 1);
+    if (last_chunk == 0) {
+      hipLaunchKernelGGL(k_plan_uniform, dim3(1), dim3(128), 0, ctx->stream, ctx->d_xrec_off, ctx->d_xrec_cap, G.n_buckets,
+                         ctx->xrec_total_blocks, blocks);
+    } else {
+      BinLog Lp{};   // (k_plan_bins reads and clears the counts of the last launch)
+      Lp.count = ctx->d_xrec_count; Lp.n_buckets = G.n_buckets; Lp.shift = G.shift; Lp.n_parts = last_parts;
+      hipLaunchKernelGGL(k_plan_bins, dim3(1), dim3(128), 0, ctx->stream, Lp, ctx->d_xrec_off, ctx->d_xrec_cap,
+                         (unsigned long long)ctx->xrec_total_blocks, (double)c / (double)last_chunk, blocks, ctx->d_xrec_want);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(ctx->d_counters + WORK_SLOT, 0, sizeof(unsigned long long), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_xrec_stats, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    A.item_lo = done; A.n_items = c; A.rec.n_parts = blocks;
+    void* args[] = {(void*)&M, (void*)&A};
+    HIPCHK(hipLaunchKernel(G.fn, dim3(blocks), dim3(G.threads), args, G.lds, ctx->stream));
+    HIPCHK(hipEventRecord(ctx->ev_xrec0, ctx->stream));
+    hipLaunchKernelGGL(k_fold_xirec, dim3(G.n_buckets * G.split), dim3(1024), G.fold_lds, ctx->stream, A.rec,
+                       reinterpret_cast<float*>(ctx->d_xI.p), A.xi, A.nRT, n_sub, G.slice_sub, G.split);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev_xrec1, ctx->stream));
+    unsigned long long st[4] = {0ull, 0ull, 0ull, 0ull};
+    int dev_err = 0;
+    HIPCHK(hipMemcpyAsync(st, ctx->d_xrec_stats, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&dev_err, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (the next launch is sized by what this one made)
+    if (dev_err) { ctx->err = "device error " + std::to_string(dev_err) + " in the commit pass"; return MCGPU_ERR_KERNEL; }
+    {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, ctx->ev_xrec0, ctx->ev_xrec1) == hipSuccess) ctx->xrec_fold_ms += ms;
+    }
+    ctx->xrec_chunks++;
+    ctx->xrec_overflow += st[0]; ctx->xrec_drained += st[1]; ctx->xrec_folded += st[2]; ctx->xrec_records += st[3];
+    done += c;
+    last_chunk = c; last_parts = blocks;
+    const double rpp = (double)st[3] / (double)c;
+    double cn = rpp > 0.0 ? 0.6 * log_records / rpp : (double)(n_total - done);
+    if (cn < 256.0) cn = 256.0;
+    chunk = cn > 4.0e18 ? n_total : (unsigned long long)cn;
+    if (n_total - done > chunk && n_total - done - chunk < chunk / 4) chunk = n_total - done;   // (a small remainder rides along)
+  }
+  return MCGPU_OK;
+}
+
 // Below this many logged crossings per flight the commit pass deposits with atomics: a flight costs its row -- 160 bytes
 // written once and gathered once per crossing -- whatever its length.  Measured at ten observers against the atomics in the
 // packed layout (4 lines per crossing; profiles/r06_xi_log_ab.log): 36 crossings per flight (ref4.1 at 60 um) 367 against
@@ -2654,6 +2875,7 @@ constexpr double XI_LOG_MIN_CROSSINGS_PER_FLIGHT = 20.0;
 // records and flights per packet; the others take what 70 % of the buffers hold at that rate -- or, where the flights
 // turn out too short for the log to pay, the rest of the pass (and of the call: *mode = 2) runs with atomics.
 static int commit_mono(mcgpu_ctx* ctx, MonoArgs A, int grid_blocks, int block_threads, int* mode) {
+  if (*mode == 3) return commit_mono_rec(ctx, A, grid_blocks, block_threads, mode);
   if (*mode != 1) return launch_mono<false>(ctx, A, grid_blocks, block_threads);
   const DevModel& M = ctx->M;
   const bool pola = ctx->lsepar_pola != 0;
@@ -2804,7 +3026,10 @@ extern "C" int mcgpu_run_mono(mcgpu_ctx* ctx, const mcgpu_mono_opts* o, double f
   A.min_active = tune("MCGPU_MIN_ACTIVE", 32, 0, 64);
   A.flags = tune("MCGPU_DIAG_FLAGS", 0, 0, 255);  // (diagnostic builds only)
   int xlog_mode = xi_log_applicable(ctx, rt1) ? 1 : 0;   // 1: the commit passes log their xI_scatt deposits (mc_xilog.hip.h folds them)
+  if (xi_rec_applicable(ctx, rt1)) xlog_mode = 3;        // 3: ... as 16-byte records in the binned log (mc_xirec.hip.h)
   ctx->xlog_chunks = 0; ctx->xlog_records = 0; ctx->xlog_flights = 0;
+  ctx->xrec_chunks = 0; ctx->xrec_buckets = 0; ctx->xrec_split = 0;
+  ctx->xrec_records = 0; ctx->xrec_folded = 0; ctx->xrec_overflow = 0; ctx->xrec_drained = 0; ctx->xrec_fold_ms = 0.0;
 
   // ---- SCOUT: find every stream's stopping index (dust_transfer.f90:526-553) ----------------
   double lim_d = std::ceil((double)o->n_phot_lim);

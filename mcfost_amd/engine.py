@@ -89,16 +89,23 @@ _lib = None
 def xi32_layout(nRT, pola, contrib):
     """The packed default-real device layout of xI_scatt the library chooses for ``nRT`` observers
     (``mcfost_amd/csrc/mc_xi32.hip.h::xi32_layout``, mirrored for the tests and the bench's accounting): default reals per
-    sub-bin, the arrangement, and the 64-byte lines one crossing's deposits touch."""
+    sub-bin, the arrangement, and the 64-byte lines one crossing's deposits touch.  ``values_per_deposit`` are the values a
+    deposit adds per observer, ``record_values`` the default reals one crossing adds to its sub-bin (all observers), and
+    ``record_log`` says whether they fit the 16-byte records of option "xi_log" = 3 (``mc_xirec.hip.h``: at most three)."""
     lines = lambda n: (n + 15) // 16
     nS = 4 if pola else 1
     if not contrib:
-        return dict(binf=16 * lines(nRT * nS), split=False, lines_touched=lines(nRT * nS), values_per_deposit=nS)
-    nA = nS - 1      # I is not stored: it is the sum of the two origins
-    l_inter, l_star, l_th = lines(nRT * (nA + 2)), lines(nRT * (nA + 1)), lines(nRT * nA) + lines(nRT)
-    if l_star + l_th < 2 * l_inter:
-        return dict(binf=16 * (l_star + lines(nRT)), split=True, lines_touched=max(l_star, l_th), values_per_deposit=nA + 1)
-    return dict(binf=16 * l_inter, split=False, lines_touched=l_inter, values_per_deposit=nA + 1)
+        lay = dict(binf=16 * lines(nRT * nS), split=False, lines_touched=lines(nRT * nS), values_per_deposit=nS)
+    else:
+        nA = nS - 1      # I is not stored: it is the sum of the two origins
+        l_inter, l_star, l_th = lines(nRT * (nA + 2)), lines(nRT * (nA + 1)), lines(nRT * nA) + lines(nRT)
+        if l_star + l_th < 2 * l_inter:
+            lay = dict(binf=16 * (l_star + lines(nRT)), split=True, lines_touched=max(l_star, l_th), values_per_deposit=nA + 1)
+        else:
+            lay = dict(binf=16 * l_inter, split=False, lines_touched=l_inter, values_per_deposit=nA + 1)
+    lay["record_values"] = nRT * lay["values_per_deposit"]
+    lay["record_log"] = lay["record_values"] <= 3
+    return lay
 
 
 def load_library(path: str = LIB_PATH):
@@ -576,7 +583,8 @@ class Engine:
 
     def set_option(self, name, value):
         """Per-context run option (``mcgpu_set_option``): "deposit" 0/1/2 = auto / HBM atomics / LDS,
-        "schedule" 0/1 = auto / single-role kernel, "speculation" 1/0 (SED mode)."""
+        "schedule" 0/1 = auto / single-role kernel, "speculation" 1/0 (SED mode), "xi_log" 0..3 (SED mode's deposits: atomics /
+        automatic / the sorted log / 16-byte records in the binned log, with "xi_rec_log_mb", "xi_rec_buckets", "xi_rec_fold_kb")."""
         self._chk(self.lib.mcgpu_set_option(self.ctx, name.encode(), C.c_int(int(value))), "mcgpu_set_option")
 
     def repartition_energie(self, lam, Tdust, E_ISM=0.0, weight=None, fetch=True):
