@@ -646,6 +646,47 @@ int mcgpu_probe_packet_rand(mcgpu_ctx *ctx, uint64_t seed, uint64_t packet,
                             int n, float *out);
 
 /*
+ * The deposit logs' staging and fold on records the caller chooses (mc_binned.hip.h run by whole workgroups; the tests
+ * give integer-valued records, whose sums are the same in any order, and compare bit for bit).
+ *   kind 0: (cell, double) records, BinLog, folded by k_fold_bins;   vals = double[n],   out = double[n_alloc]
+ *   kind 1: the SED commit pass's 16-byte records, XiRecLog, folded by k_fold_xirec (nRT 1..3 observers without Stokes
+ *           tracking, contrib = lsepar_contrib);   vals = float[n][3],   out = float[n_alloc][binf] in the packed layout,
+ *           keys[i] = sub-bin | flag_star << 31
+ * Schedule: the launch has T = grid_blocks * block_threads threads (block_threads a multiple of 64, <= 768); its global
+ * thread g handles record r * T + g in round r; keys[i] = 0xFFFFFFFF leaves that lane inactive in that round.  n is a
+ * multiple of T.  The R = n / T rounds are cut into n_launches consecutive segments, launch j (0-based) running the rounds
+ * [R j / n_launches, R (j + 1) / n_launches).  The log has total_blocks blocks of 64 records, n_buckets buckets of
+ * 2^shift places; it is filled with records that must never be read (key 0x7FFFFFFF, values 1e30) first.  Launch 0 is
+ * planned by k_plan_uniform, every later one by k_plan_bins from the counts of the launch before, with growth = its records
+ * over that launch's (1 where that launch had none); every launch is followed by its fold, with the statistics and the
+ * counts handled as the thermal step (kind 0) and the commit pass (kind 1) handle them.
+ * Fold: fold_threads (a multiple of 64, <= 1024) per workgroup; split_or_slice_sub is `split` for kind 0 and `slice_sub`
+ * for kind 1 (split = ceil(2^shift / slice_sub), as the commit pass derives it).
+ * out is in/out: the n_out <= n_alloc places the log serves, then slack that must come back unchanged.  Kind 0: every
+ * key < n_out.  Kind 1: (key & 0x7FFFFFFF) < n_alloc; sink and fold both drop a key >= n_out.
+ * Returned: stats[4] summed over the launches = blocks that overflowed their part, records drained at the end of a launch,
+ * records the folds summed, records made; off / cap [n_launches][n_buckets]: every launch's plan; counts_left[n_launches]:
+ * the block counts that were not zero when the launch's plan had run.
+ * MCGPU_ERR_ARG (nothing launched): a staging or a fold slice that does not fit in LDS, a key beyond the array or the buckets,
+ * any other bad argument.  The probe owns and frees its device buffers; the context's logs and options are untouched.
+ */
+int mcgpu_probe_bin_stage(mcgpu_ctx *ctx, int kind, uint64_t n, const uint32_t *keys, const void *vals, int grid_blocks,
+                          int block_threads, int n_buckets, int shift, uint64_t total_blocks, int n_launches,
+                          int fold_threads, int split_or_slice_sub, int nRT, int contrib, uint64_t n_out, uint64_t n_alloc,
+                          void *out, uint64_t stats[4], uint32_t *off, uint32_t *cap, uint32_t *counts_left);
+
+/*
+ * The sorted log's fold (option "xi_log" = 1 / 2: hipCUB's radix sort + k_xi_segfold) on records the caller chooses:
+ * record i = (keys[i] = sub-bin | flag_star << 31, flight[i] < n_flights, path length l[i]); rows[n_flights][nv * nRT]
+ * the flights' deposit weights (nv = 4 with pola, else 1); xI[n_bins][binf] in/out in the packed layout of
+ * (nRT, pola, contrib).  The sort's key bits and the unused entries' key (*sentinel, may be NULL) come from the function
+ * the commit pass uses; an entry with that key is one a wave reserved and did not use.  n = 0: the sentinel alone.
+ */
+int mcgpu_probe_xi_sort_fold(mcgpu_ctx *ctx, uint64_t n, const uint32_t *keys, const uint32_t *flight, const float *l,
+                             uint32_t n_flights, const float *rows, int nRT, int pola, int contrib, uint32_t n_bins,
+                             float *xI, uint32_t *sentinel);
+
+/*
  * lvariable_dust (dust settling etc.; mem.f90:213-244): the opacity and re-emission tables gain the cell axis
  * p_n_cells and the loop reads them with p_icell (optical_depth.f90:100-102, radiation_field.f90:47-53,
  * dust_transfer.f90:1284, thermal_emission.f90:659-771).  Call after mcgpu_set_opacity and mcgpu_set_thermal, with

@@ -34,6 +34,7 @@
 #include <chrono>
 #include "host_tail.h"
 #include "mc_xilog.hip.h"
+#include "mc_stage_probe.hip.h"
 
 using namespace mcgpu;
 
@@ -2870,6 +2871,15 @@ static int commit_mono_rec(mcgpu_ctx* ctx, MonoArgs A, int grid_blocks, int bloc
 // 384 ms; 6 per flight (0.3 um) 633 against 534 ms; 2.2 per flight (1 um) 1.70 against 1.30 s.
 constexpr double XI_LOG_MIN_CROSSINGS_PER_FLIGHT = 20.0;
 
+// The sorted log's key: the sort looks at the low `end_bit` bits, and the unused entries' key (the sentinel),
+// 2^end_bit - 1 >= n_bins, sorts last.  false: too many sub-bins for a 31-bit key (bit 31 is flag_star).
+static bool xi_log_key_bits(unsigned int n_bins, int* end_bit) {
+  int e = 1;
+  while (e < 31 && (1u << e) <= n_bins) ++e;
+  *end_bit = e;
+  return (1u << e) - 1u >= n_bins;
+}
+
 // One commit pass (the work items [0, A.n_items) of `A`): plainly, or -- `*mode` = 1: with its deposits logged, in launches
 // sized for the log, each followed by the sort and the fold of what it logged.  The first launch is short and measures
 // records and flights per packet; the others take what 70 % of the buffers hold at that rate -- or, where the flights
@@ -2884,8 +2894,7 @@ static int commit_mono(mcgpu_ctx* ctx, MonoArgs A, int grid_blocks, int block_th
   if (rc) return rc;
   const unsigned int n_bins = (unsigned int)((size_t)M.n_cells * A.n_theta_rt * A.n_az_rt);
   int end_bit = 1;
-  while (end_bit < 31 && (1u << end_bit) <= n_bins) ++end_bit;   // the unused entries' key, 2^end_bit - 1 >= n_bins, sorts last
-  if ((1u << end_bit) - 1u < n_bins) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "xI log: too many sub-bins for a 31-bit key");
+  if (!xi_log_key_bits(n_bins, &end_bit)) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "xI log: too many sub-bins for a 31-bit key");
   A.log_keys = ctx->d_xlog_keys[0]; A.log_vals = ctx->d_xlog_vals[0]; A.log_rows = ctx->d_xlog_rows; A.log_ctl = ctx->d_xlog_ctl;
   A.log_cap = xlog_cap(ctx); A.rows_cap = xlog_rows_cap(ctx); A.log_sentinel = (1u << end_bit) - 1u;
   const int nv = pola ? 4 : 1;
@@ -4153,6 +4162,207 @@ extern "C" int mcgpu_probe_packet_rand(mcgpu_ctx* ctx, uint64_t seed, uint64_t p
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(d.get(out, n));
+  return MCGPU_OK;
+}
+
+// ---- exact-sum probes of the deposit logs (mc_stage_probe.hip.h; tests/test_deposit_log_exact.py) ------------------------
+// The launches of mcgpu_probe_bin_stage for one value type: plan -> staging kernel -> fold per launch, as launch_binned
+// (`stats_per_launch` false: the statistics run on) and commit_mono_rec (true: cleared in front of every launch) do it.
+// `fold(L)` launches the fold of a launch; `folded_on_host`: k_fold_bins does not count what it sums, the records it
+// takes are min(count, cap) blocks of every part.
+template <typename V, typename LOG, typename SINK, typename IN, typename FOLD>
+static int probe_stage_launches(mcgpu_ctx* ctx, LOG L, const SINK& E, const unsigned int* d_keys, const IN* d_vals,
+                                const uint32_t* h_keys, uint64_t n, int grid_blocks, int block_threads, unsigned long long total_blocks,
+                                int n_launches, unsigned int* d_off, unsigned int* d_cap, unsigned int* d_count, double* d_want,
+                                bool stats_per_launch, bool folded_on_host, FOLD fold, uint64_t* stats, uint32_t* off, uint32_t* cap,
+                                uint32_t* counts_left) {
+  const int nb = L.n_buckets;
+  const size_t lds = (bin_lds_bytes_of<V>(nb) + 15) / 16 * 16;
+  const void* fn = (const void*)k_probe_bin_stage<V, LOG, SINK, IN>;
+  HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const uint64_t T = (uint64_t)grid_blocks * block_threads, R = n / T;
+  const size_t n_count = (size_t)nb * grid_blocks;
+  std::vector<unsigned int> h_count(n_count), h_cap(nb), h_off(nb);
+  unsigned long long st[4] = {0ull, 0ull, 0ull, 0ull}, sum[4] = {0ull, 0ull, 0ull, 0ull};
+  if (total_blocks) hipLaunchKernelGGL((k_probe_stage_fill<LOG>), dim3(256), dim3(256), 0, ctx->stream, L, (size_t)total_blocks * BIN_H);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(d_count, 0, n_count * sizeof(unsigned int), ctx->stream));
+  HIPCHK(hipMemsetAsync(L.stats, 0, sizeof(st), ctx->stream));
+  uint64_t last_made = 0;
+  unsigned long long folded_host = 0ull;
+  for (int j = 0; j < n_launches; ++j) {
+    const uint64_t r0 = R * (uint64_t)j / (uint64_t)n_launches, r1 = R * (uint64_t)(j + 1) / (uint64_t)n_launches;
+    uint64_t made = 0;
+    for (uint64_t i = r0 * T; i < r1 * T; ++i) made += h_keys[i] != STAGE_PROBE_NONE;
+    if (j == 0) {
+      hipLaunchKernelGGL(k_plan_uniform, dim3(1), dim3(128), 0, ctx->stream, d_off, d_cap, nb, total_blocks, grid_blocks);
+    } else {
+      BinLog Lp{};   // (k_plan_bins reads and clears the counts of the last launch)
+      Lp.count = d_count; Lp.n_buckets = nb; Lp.shift = L.shift; Lp.n_parts = grid_blocks;
+      const double growth = last_made ? (double)made / (double)last_made : 1.0;
+      hipLaunchKernelGGL(k_plan_bins, dim3(1), dim3(128), 0, ctx->stream, Lp, d_off, d_cap, total_blocks, growth, grid_blocks, d_want);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_off.data(), d_off, nb * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_cap.data(), d_cap, nb * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_count.data(), d_count, n_count * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    // (the plan is checked here too: a region beyond the log would be written by the launch)
+    for (int b = 0; b < nb; ++b)
+      if ((unsigned long long)h_off[b] + (unsigned long long)h_cap[b] * grid_blocks > total_blocks)
+        return fail(ctx, MCGPU_ERR_KERNEL, "mcgpu_probe_bin_stage: the plan puts a region beyond the log");
+    counts_left[j] = 0;
+    for (size_t i = 0; i < n_count; ++i) counts_left[j] += h_count[i] != 0u;
+    memcpy(off + (size_t)j * nb, h_off.data(), nb * sizeof(uint32_t));
+    memcpy(cap + (size_t)j * nb, h_cap.data(), nb * sizeof(uint32_t));
+    if (stats_per_launch) HIPCHK(hipMemsetAsync(L.stats, 0, sizeof(st), ctx->stream));
+    hipLaunchKernelGGL((k_probe_bin_stage<V, LOG, SINK, IN>), dim3(grid_blocks), dim3(block_threads), lds, ctx->stream, L, E, d_keys,
+                       d_vals, (unsigned long long)(r0 * T), (int)(r1 - r0));
+    HIPCHK(hipGetLastError());
+    fold(L);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(st, L.stats, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_count.data(), d_count, n_count * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int q = 0; q < 4; ++q) sum[q] = stats_per_launch ? sum[q] + st[q] : st[q];
+    if (folded_on_host)
+      for (int b = 0; b < nb; ++b)
+        for (int p = 0; p < grid_blocks; ++p) {
+          const unsigned int c = h_count[(size_t)b * grid_blocks + p];
+          folded_host += (unsigned long long)(c < h_cap[b] ? c : h_cap[b]) * BIN_H;
+        }
+    last_made = made;
+  }
+  if (folded_on_host) sum[2] = folded_host;
+  for (int q = 0; q < 4; ++q) stats[q] = sum[q];
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_probe_bin_stage(mcgpu_ctx* ctx, int kind, uint64_t n, const uint32_t* keys, const void* vals, int grid_blocks,
+                                     int block_threads, int n_buckets, int shift, uint64_t total_blocks, int n_launches,
+                                     int fold_threads, int split_or_slice_sub, int nRT, int contrib, uint64_t n_out, uint64_t n_alloc,
+                                     void* out, uint64_t stats[4], uint32_t* off, uint32_t* cap, uint32_t* counts_left) {
+  if (!ctx) return MCGPU_ERR_ARG;
+  const char* const bad = "mcgpu_probe_bin_stage: bad argument";
+  if ((kind != 0 && kind != 1) || !keys || !vals || !out || !stats || !off || !cap || !counts_left) return fail(ctx, MCGPU_ERR_ARG, bad);
+  if (grid_blocks < 1 || grid_blocks > 4096 || block_threads < 64 || block_threads > 768 || block_threads % 64) return fail(ctx, MCGPU_ERR_ARG, bad);
+  if (n_buckets < 1 || n_buckets > BIN_MAX_BUCKETS || shift < 0 || shift > 20 || n_launches < 1 || n_launches > 64) return fail(ctx, MCGPU_ERR_ARG, bad);
+  if (total_blocks > (1ull << 18) || fold_threads < 64 || fold_threads > 1024 || fold_threads % 64) return fail(ctx, MCGPU_ERR_ARG, bad);
+  const uint64_t T = (uint64_t)grid_blocks * block_threads;
+  if (n < 1 || n > (1ull << 26) || n % T) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_bin_stage: the records are whole rounds of the launch's threads");
+  if (n_out < 1 || n_out > n_alloc || n_alloc > (1ull << 24)) return fail(ctx, MCGPU_ERR_ARG, bad);
+  // every record lands in memory the probe owns: a cell of the array (kind 1: a row of the allocation, which sink and
+  // fold drop beyond n_out), in a bucket the staging has
+  const uint64_t key_end = kind == 0 ? n_out : n_alloc;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (keys[i] == STAGE_PROBE_NONE) continue;
+    const uint32_t k = kind == 0 ? keys[i] : (keys[i] & 0x7FFFFFFFu);
+    if (k >= key_end || (k >> shift) >= (uint32_t)n_buckets) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_bin_stage: a key beyond the array or the buckets");
+  }
+  const size_t lds_cap = 160 * 1024 - 512;
+  HIPCHK(hipSetDevice(ctx->device));
+  DevArr<unsigned int> d_keys, d_count, d_off, d_cap;
+  DevArr<unsigned long long> d_stats;
+  DevArr<double> d_want;
+  HIPCHK(d_keys.resize(n)); HIPCHK(d_keys.put(keys, n));
+  HIPCHK(d_count.resize((size_t)n_buckets * grid_blocks)); HIPCHK(d_off.resize(n_buckets)); HIPCHK(d_cap.resize(n_buckets));
+  HIPCHK(d_stats.resize(4)); HIPCHK(d_want.resize(n_buckets));
+  const size_t log_records = (size_t)(total_blocks ? total_blocks : 1) * BIN_H;
+  if (kind == 0) {
+    const int split = split_or_slice_sub;
+    const size_t fold_lds = sizeof(double) << shift;
+    if (split < 1 || split > 4096 || fold_lds > lds_cap || bin_lds_bytes_of<double>(n_buckets) + 16 > lds_cap)
+      return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_bin_stage: the staging or the fold's slice does not fit in LDS");
+    DevArr<double> d_vals, d_logv, d_E;
+    DevArr<unsigned int> d_logk;
+    HIPCHK(d_vals.resize(n)); HIPCHK(d_vals.put((const double*)vals, n));
+    HIPCHK(d_logv.resize(log_records)); HIPCHK(d_logk.resize(log_records));
+    HIPCHK(d_E.resize(n_alloc)); HIPCHK(d_E.put((const double*)out, n_alloc));
+    BinLog L{};
+    L.keys = d_logk; L.vals = d_logv; L.count = d_count; L.off = d_off; L.cap = d_cap; L.stats = d_stats;
+    L.n_buckets = n_buckets; L.shift = shift; L.n_parts = grid_blocks;
+    HIPCHK(hipFuncSetAttribute((const void*)k_fold_bins, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_lds));
+    double* const E = d_E;
+    auto fold = [&](const BinLog& Lf) {
+      hipLaunchKernelGGL(k_fold_bins, dim3(n_buckets * split), dim3(fold_threads), fold_lds, ctx->stream, Lf, E, (int)n_out, split);
+    };
+    const int rc = probe_stage_launches<double>(ctx, L, E, d_keys.p, d_vals.p, keys, n, grid_blocks, block_threads, total_blocks, n_launches,
+                                                d_off.p, d_cap.p, d_count.p, d_want.p, false, true, fold, stats, off, cap, counts_left);
+    if (rc) return rc;
+    // (launch_binned: the counts of the last chunk are cleared for the next launch)
+    HIPCHK(hipMemsetAsync(d_count, 0, (size_t)n_buckets * grid_blocks * sizeof(unsigned int), ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(d_E.get((double*)out, n_alloc));
+    return MCGPU_OK;
+  }
+  const int slice_sub = split_or_slice_sub;
+  if (nRT < 1 || nRT > XIREC_MAX_V || !xirec_applies(nRT, false, contrib != 0)) return fail(ctx, MCGPU_ERR_ARG, bad);
+  const Xi32Lay xi = xi32_layout(nRT, false, contrib != 0);
+  if (slice_sub < 1 || (unsigned long long)slice_sub > (1ull << shift)) return fail(ctx, MCGPU_ERR_ARG, bad);
+  const int split = (int)(((1ull << shift) + (unsigned long long)slice_sub - 1) / (unsigned long long)slice_sub);
+  const size_t fold_lds = (size_t)slice_sub * xirec_slots(xi, nRT) * sizeof(float);
+  if (fold_lds > lds_cap || bin_lds_bytes_of<XiRec>(n_buckets) + 16 > lds_cap || (unsigned long long)n_buckets * split > (1ull << 22))
+    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_bin_stage: the staging or the fold's slice does not fit in LDS");
+  DevArr<float> d_vals, d_xI;
+  DevArr<XiRec> d_log;
+  HIPCHK(d_vals.resize(3 * n)); HIPCHK(d_vals.put((const float*)vals, 3 * n));
+  HIPCHK(d_log.resize(log_records));
+  HIPCHK(d_xI.resize(n_alloc * xi.binf)); HIPCHK(d_xI.put((const float*)out, n_alloc * xi.binf));
+  XiRecLog L{};
+  L.vals = d_log; L.keys = nullptr; L.count = d_count; L.off = d_off; L.cap = d_cap; L.stats = d_stats;
+  L.n_buckets = n_buckets; L.shift = shift; L.n_parts = grid_blocks;
+  const XiRecSink K = {d_xI.p, xi, nRT, (unsigned int)n_out};
+  HIPCHK(hipFuncSetAttribute((const void*)k_fold_xirec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_lds));
+  float* const xI = d_xI;
+  auto fold = [&](const XiRecLog& Lf) {
+    hipLaunchKernelGGL(k_fold_xirec, dim3(n_buckets * split), dim3(fold_threads), fold_lds, ctx->stream, Lf, xI, xi, nRT,
+                       (unsigned int)n_out, slice_sub, split);
+  };
+  const int rc = probe_stage_launches<XiRec>(ctx, L, K, d_keys.p, d_vals.p, keys, n, grid_blocks, block_threads, total_blocks, n_launches,
+                                             d_off.p, d_cap.p, d_count.p, d_want.p, true, false, fold, stats, off, cap, counts_left);
+  if (rc) return rc;
+  HIPCHK(d_xI.get((float*)out, n_alloc * xi.binf));
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_probe_xi_sort_fold(mcgpu_ctx* ctx, uint64_t n, const uint32_t* keys, const uint32_t* flight, const float* l,
+                                        uint32_t n_flights, const float* rows, int nRT, int pola, int contrib, uint32_t n_bins,
+                                        float* xI, uint32_t* sentinel) {
+  if (!ctx) return MCGPU_ERR_ARG;
+  const char* const bad = "mcgpu_probe_xi_sort_fold: bad argument";
+  if (nRT < 1 || nRT > 64 || n_bins < 1 || n > (1ull << 26)) return fail(ctx, MCGPU_ERR_ARG, bad);
+  int end_bit = 1;
+  if (!xi_log_key_bits(n_bins, &end_bit)) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_xi_sort_fold: too many sub-bins for a 31-bit key");
+  const uint32_t unused = (1u << end_bit) - 1u;
+  if (sentinel) *sentinel = unused;
+  if (n == 0) return MCGPU_OK;   // (asked for the sentinel alone)
+  if (!keys || !flight || !l || !rows || !xI || n_flights < 1) return fail(ctx, MCGPU_ERR_ARG, bad);
+  const int nv = pola ? 4 : 1;
+  const Xi32Lay xi = xi32_layout(nRT, pola != 0, contrib != 0);
+  std::vector<unsigned long long> h_vals(n);
+  for (uint64_t i = 0; i < n; ++i) {
+    if (flight[i] >= n_flights || ((keys[i] & 0x7FFFFFFFu) >= n_bins && keys[i] != unused))
+      return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_xi_sort_fold: a flight without a row, or a key that is neither a sub-bin nor the sentinel");
+    uint32_t lb;
+    memcpy(&lb, &l[i], sizeof(lb));
+    h_vals[i] = ((unsigned long long)lb << 32) | flight[i];
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  DevArr<unsigned int> d_keys[2];
+  DevArr<unsigned long long> d_vals[2];
+  DevArr<float> d_rows, d_xI;
+  DevArr<char> d_temp;
+  const size_t row_floats = (size_t)nv * nRT;
+  for (int i = 0; i < 2; ++i) { HIPCHK(d_keys[i].resize(n)); HIPCHK(d_vals[i].resize(n)); }
+  HIPCHK(d_keys[0].put(keys, n)); HIPCHK(d_vals[0].put(h_vals.data(), n));
+  HIPCHK(d_rows.resize(n_flights * row_floats)); HIPCHK(d_rows.put(rows, n_flights * row_floats));
+  HIPCHK(d_xI.resize((size_t)n_bins * xi.binf)); HIPCHK(d_xI.put(xI, (size_t)n_bins * xi.binf));
+  HIPCHK(d_temp.resize(xi_sort_temp_bytes(n, end_bit)));
+  const int e = xi_sort_fold(ctx->stream, d_keys[0], d_vals[0], d_keys[1], d_vals[1], (size_t)n, end_bit, d_temp, d_temp.n, d_rows, nRT, nv,
+                             contrib != 0, n_bins, d_xI, xi);
+  if (e != (int)hipSuccess) { ctx->err = std::string("mcgpu_probe_xi_sort_fold: sort / fold: ") + hipGetErrorString((hipError_t)e); return MCGPU_ERR_HIP; }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(d_xI.get(xI, (size_t)n_bins * xi.binf));
   return MCGPU_OK;
 }
 

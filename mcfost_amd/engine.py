@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "mcgpu_set_grid_sph", "mcgpu_temp_approx_diffusion_vertical", "mcgpu_set_mrw", "mcgpu_fetch_radiation_field", "mcgpu_set_variable_dust", "mcgpu_rt1_stars_map_sed", "mcgpu_define_dark_zone", "mcgpu_init_reemission", "mcgpu_multi_create", "mcgpu_multi_destroy", "mcgpu_multi_size", "mcgpu_multi_ctx", "mcgpu_multi_last_error",
     "mcgpu_repartition_energie", "mcgpu_opacity", "mcgpu_set_variable_dust_s11", "mcgpu_set_scattering_method1", "mcgpu_set_rt2", "mcgpu_fetch_I_spec", "mcgpu_rt1_stars_map_image", "mcgpu_set_I_spec", "mcgpu_rt2_source", "mcgpu_rt2_dust_map", "mcgpu_rt2_image", "mcgpu_shard_packets", "mcgpu_multi_run_thermal", "mcgpu_multi_run_mono", "mcgpu_multi_run_sed", "mcgpu_multi_rccl_ranks", "mcgpu_multi_create_ex", "mcgpu_multi_reductions", "mcgpu_set_mrw_exit_spectrum", "mcgpu_voronoi_tesselation", "mcgpu_build_ksca_CDF", "mcgpu_init_reemission_ex", "mcgpu_tau_maps",
     "mcgpu_set_nlte", "mcgpu_init_reemission_nlte", "mcgpu_set_J0", "mcgpu_temp_finale_nlte", "mcgpu_set_Tdust_1grain",
-    "mcgpu_probe_reemission_nlte",
+    "mcgpu_probe_reemission_nlte", "mcgpu_probe_bin_stage", "mcgpu_probe_xi_sort_fold",
 )
 
 
@@ -106,6 +106,26 @@ def xi32_layout(nRT, pola, contrib):
     lay["record_values"] = nRT * lay["values_per_deposit"]
     lay["record_log"] = lay["record_values"] <= 3
     return lay
+
+
+def xi32_offset(nRT, pola, contrib, q, flux_type):
+    """Where flux type ``flux_type`` (0-based index into N_type_flux) of observer ``q`` lies inside a sub-bin of the packed
+    layout (``mc_xi32.hip.h::xi32_offset``, mirrored): -1 for a type no deposit reaches, -2 for I where it is the sum of the
+    two origins (``contrib``)."""
+    lines = lambda n: (n + 15) // 16
+    nS = 4 if pola else 1
+    if not contrib:
+        return q * nS + flux_type if flux_type < nS else -1
+    nA = nS - 1
+    split = xi32_layout(nRT, pola, contrib)["split"]
+    sA = nA if split else nA + 2
+    if flux_type < nS:
+        return -2 if flux_type == 0 else q * sA + flux_type - 1
+    if flux_type == nS + 1:       # scattered stellar light
+        return nRT * nA + q if split else q * sA + nA
+    if flux_type == nS + 3:       # scattered thermal light
+        return 16 * lines(nRT * (nA + 1)) + q if split else q * sA + nA + 1
+    return -1
 
 
 def load_library(path: str = LIB_PATH):
@@ -915,6 +935,58 @@ class Engine:
         o = (C.c_uint32 * 4)()
         self._chk(self.lib.mcgpu_probe_philox(self.ctx, c, k, o), "mcgpu_probe_philox")
         return [int(v) for v in o]
+
+    def probe_bin_stage(self, kind, keys, vals, out, grid_blocks, block_threads, n_buckets, shift, total_blocks, n_out,
+                        n_launches=1, fold_threads=1024, split=1, slice_sub=None, nRT=1, contrib=False):
+        """The deposit logs' staging and fold on chosen records (``mcgpu_probe_bin_stage``; the schedule and the arguments
+        are described in ``include/mcgpu.h``).  ``kind`` 0: ``vals`` float64 ``[n]``, ``out`` float64 ``[n_alloc]``, fold
+        geometry ``split``; ``kind`` 1: ``vals`` float32 ``[n, 3]``, ``out`` float32 ``[n_alloc, binf]``, fold geometry
+        ``slice_sub``.  ``out`` is not modified.  Returns ``dict(out, overflow, drained, folded, made, off, cap,
+        counts_left)`` with ``off`` / ``cap`` ``[n_launches, n_buckets]`` and ``counts_left`` ``[n_launches]``."""
+        k = _a(keys, np.uint32)
+        n = k.size
+        if kind == 0:
+            v, o = _a(vals, np.float64), np.array(out, dtype=np.float64, order="C")
+            assert v.shape == (n,) and o.ndim == 1
+            geom = split
+        else:
+            v, o = _a(vals, np.float32), np.array(out, dtype=np.float32, order="C")
+            assert v.shape == (n, 3) and o.ndim == 2 and o.shape[1] == xi32_layout(nRT, False, contrib)["binf"]
+            geom = (1 << shift) if slice_sub is None else slice_sub
+        stats = np.zeros(4, np.uint64)
+        off, cap = np.zeros((n_launches, n_buckets), np.uint32), np.zeros((n_launches, n_buckets), np.uint32)
+        left = np.zeros(n_launches, np.uint32)
+        self._chk(self.lib.mcgpu_probe_bin_stage(
+            self.ctx, C.c_int(kind), C.c_uint64(n), _p(k, C.c_uint32), v.ctypes.data_as(C.c_void_p), C.c_int(grid_blocks),
+            C.c_int(block_threads), C.c_int(n_buckets), C.c_int(shift), C.c_uint64(total_blocks), C.c_int(n_launches),
+            C.c_int(fold_threads), C.c_int(geom), C.c_int(nRT), C.c_int(int(contrib)), C.c_uint64(n_out),
+            C.c_uint64(o.shape[0]), o.ctypes.data_as(C.c_void_p), _p(stats, C.c_uint64), _p(off, C.c_uint32),
+            _p(cap, C.c_uint32), _p(left, C.c_uint32)), "mcgpu_probe_bin_stage")
+        return dict(out=o, overflow=int(stats[0]), drained=int(stats[1]), folded=int(stats[2]), made=int(stats[3]),
+                    off=off, cap=cap, counts_left=left)
+
+    def xi_log_sentinel(self, n_bins):
+        """The key of the sorted log's unused entries for ``n_bins`` sub-bins, as the commit pass computes it."""
+        s = C.c_uint32(0)
+        self._chk(self.lib.mcgpu_probe_xi_sort_fold(self.ctx, C.c_uint64(0), None, None, None, C.c_uint32(0), None, C.c_int(1),
+                                                    C.c_int(0), C.c_int(0), C.c_uint32(n_bins), None, C.byref(s)),
+                  "mcgpu_probe_xi_sort_fold")
+        return int(s.value)
+
+    def probe_xi_sort_fold(self, keys, flight, l, rows, nRT, pola, contrib, n_bins, xI):
+        """The sorted log's fold on chosen records (``mcgpu_probe_xi_sort_fold``): ``keys`` uint32 ``[n]`` (sub-bin |
+        flag_star << 31, or the sentinel), ``flight`` ``[n]``, ``l`` float32 ``[n]``, ``rows`` float32
+        ``[n_flights, nv * nRT]``; returns ``xI`` float32 ``[n_bins, binf]`` plus the sums (``xI`` is not modified)."""
+        k, f, ll = _a(keys, np.uint32), _a(flight, np.uint32), _a(l, np.float32)
+        r = _a(rows, np.float32)
+        o = np.array(xI, dtype=np.float32, order="C")
+        assert f.shape == k.shape == ll.shape and r.ndim == 2 and r.shape[1] == (4 if pola else 1) * nRT
+        assert o.shape == (n_bins, xi32_layout(nRT, pola, contrib)["binf"])
+        self._chk(self.lib.mcgpu_probe_xi_sort_fold(
+            self.ctx, C.c_uint64(k.size), _p(k, C.c_uint32), _p(f, C.c_uint32), _p(ll, C.c_float), C.c_uint32(r.shape[0]),
+            _p(r, C.c_float), C.c_int(nRT), C.c_int(int(pola)), C.c_int(int(contrib)), C.c_uint32(n_bins), _p(o, C.c_float),
+            None), "mcgpu_probe_xi_sort_fold")
+        return o
 
     def probe_packet_rand(self, seed, packet, n):
         out = np.zeros(n, np.float32)

@@ -32,7 +32,7 @@ def _layout(lib, nRT, pola, contrib):
 
 
 def test_layout_invariants_and_python_mirror(lib):
-    from mcfost_amd.engine import xi32_layout
+    from mcfost_amd.engine import xi32_layout, xi32_offset
     for nRT in list(range(1, 41)) + [64, 100]:
         for pola in (False, True):
             for contrib in (False, True):
@@ -45,6 +45,7 @@ def test_layout_invariants_and_python_mirror(lib):
                 for q in range(nRT):
                     for t in range(ntf):
                         o = lib.xi32_probe_offset(nRT, int(pola), int(contrib), q, t)
+                        assert xi32_offset(nRT, pola, contrib, q, t) == o, (nRT, pola, contrib, q, t)   # (the mirror in engine.py)
                         reachable = t < nS or t in (nS + 1, nS + 3)
                         if contrib and t == 0:
                             assert o == -2
