@@ -447,6 +447,156 @@ __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, cons
 }
 
 // ---------------------------------------------------------------------------------------------
+// The flying loop's crossing, run UNDER the flight predicate (the flying waves of every 2D instantiation of roles_body
+// but PARAM; serving waves, k_tail, the host tail and the OUT form keep fly_step_2d, which is this function's
+// specification: tests/emu/emu_fly_visit.cpp walks both, bit for bit).
+// fly_step_2d lets every lane compute and commits by selects on go / move / active; its loop's time is its instruction
+// count, and two thirds of that count are not arithmetic.  Here the whole crossing sits in ONE region under the flight
+// predicate p.st == S_FLIGHT -- a lane that does not fly keeps its registers by construction; p.st is written only when
+// a flight ends, so the predicate is one compare per iteration -- and the events that end a flight commit in their own
+// rare branches: the exit / the star's cell (once per packet), the stop (once per flight; it had a branch already, for
+// its division) and, with DARK, the mirror.  What is left is the fall-through: the lanes that move to the next cell
+// commit without a select.  (A `bool flying` carried by the loop instead of the compare: the compiler keeps it as a
+// byte in a VGPR, or, set from p.st behind the crossing, as a mask at +3 SALU for -1 VALU: DESIGN.md section 3.)
+// The crossings are counted by the caller, once per visit, from what the packet's own counter gained.
+//
+// fly_geom_2d: sections 1-3 of fly_step_2d (radial wall, vertical wall, nearest wall, zj of the end point), expression
+// for expression, the three rounding-level fix-ups (-> GRID_PREC) as selects.  Returns which of them applied -- bit 0:
+// s1 == 0, bit 1: t < 0, bit 2: z1 == 0 (for tests/emu/emu_fly_visit.cpp; the kernels do not read it).
+__device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, const Flight& p, double& l_out, double& z1_out,
+                                            int& ri1_out, int& zj1_out) {
+  const int n_rad = M.n_rad, nz = M.nz;
+  const double cp = 1.0 + GRID_PREC;
+  const int ri0 = p.ri, zj0 = p.zj;
+  const double x0 = p.x, y0 = p.y, z0 = p.z, u = p.u, v = p.v, w = p.w;
+  const bool top = (zj0 == nz + 1);
+  const bool hole = (ri0 == 0);
+  const RowT& R0 = T.row[ri0];
+  int fix = 0;
+
+  // 1) radial wall
+  const double r_2 = x0 * x0 + y0 * y0;
+  const double dot = x0 * u + y0 * v;
+  const double b = dot * p.inv_a;
+  const double c_in = (r_2 - R0.rl_in) * p.inv_a;
+  const double c_out = (r_2 - R0.rl_out) * p.inv_a;
+  const double bb = b * b;
+  const double d_in = bb - c_in;
+  const double d_out = fmax(bb - c_out, 0.0);
+  const bool use_in = hole || ((dot < 0.0) && !(d_in < 0.0));
+  const double delta = use_in ? d_in : d_out;
+  const int delta_rad = (use_in && !hole) ? -1 : 1;
+  const double rac = sqrt_nonneg(delta);
+  const double s1 = (-b - rac) * cp, s2 = (-b + rac) * cp;
+  fix |= (s1 == 0.0) ? 1 : 0;
+  const double s_pos = (s1 == 0.0) ? GRID_PREC : s1;
+  const double s = (hole || (s1 < 0.0)) ? s2 : s_pos;
+
+  // 2) vertical wall
+  const double dz = w * z0;
+  const bool away = dz > 0.0;
+  const bool flip = !away && (zj0 == 1);
+  const int jm = away ? zj0 : (zj0 == 1 ? 1 : zj0 - 1);
+  const bool below = jm < nz;
+  double zmag = (double)(below ? jm : 1) * *(below ? &R0.ch : &R0.zmax);
+  zmag = __builtin_fma(zmag, __longlong_as_double(away ? 0x3D06800000000000ll : (long long)0xBD06800000000000ull), zmag);
+  zmag = (away && top) ? 1.0e10 : zmag;
+  const bool neg = (z0 < 0.0) != flip;
+  const double zl = __longlong_as_double(__double_as_longlong(zmag) | (neg ? (long long)0x8000000000000000ull : 0ll));
+  const int delta_zj = away ? (top ? 0 : 1) : ((zj0 == 1) ? 1 : -1);
+  double t = (zl - z0) * p.inv_w;
+  fix |= ((t < 0.0) && !((dz == 0.0) || hole)) ? 2 : 0;
+  t = (t < 0.0) ? GRID_PREC : t;
+  t = ((dz == 0.0) || hole) ? 1.0e10 : t;
+
+  // 3) nearest wall
+  const bool rad = (s < t);
+  const double l = fmin(s, t);
+  double z1 = nd_add(z0, nd_mul(l, w));
+  const int ri1 = rad ? ri0 + delta_rad : ri0;
+  const double qd = fabs(z1) * T.row[ri1].rzn;
+  const double fl = floor(qd);
+  int zjr = (int)fmin(fl, (double)nz) + 1;
+  const bool rad_in = rad && (ri1 >= 1) && (ri1 <= n_rad);
+  const double fr = qd - fl;
+  if (__builtin_expect(rad_in && (fr < 1.0e-4 || fr > 1.0 - 1.0e-4), 0)) {  // (rare)
+    const int zq = zj_from_z_real(T, nz, fabs(z1), ri1);
+    zjr = zq > nz ? nz + 1 : zq;
+  }
+  zjr = (ri1 > n_rad) ? zj0 : zjr;
+  zj1_out = rad ? zjr : zj0 + delta_zj;
+  fix |= (z1 == 0.0) ? 4 : 0;
+  z1 = (z1 == 0.0) ? GRID_PREC : z1;
+  l_out = l; z1_out = z1; ri1_out = ri1;
+  return fix;
+}
+
+// One crossing of the lanes in flight.  The caller counts the crossings (p.pk_cross), the packets killed at the star's
+// cell (p.st == S_EMIT) and tests the crossing counter for a runaway, once per visit.
+template <bool DARK, bool LDSE, bool MRW = false, bool VAR = false>
+__device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& M, const RunArgs& A, double* E_lds, Flight& p,
+                                                  unsigned int& c_dark) {
+  static_assert((1.0 + GRID_PREC) - 1.0 == 0x1.68p-47 && 1.0 - (1.0 - GRID_PREC) == 0x1.68p-47, "grid_prec is not 45 ulp");
+  if (p.st == S_FLIGHT) {
+    const int n_rad = M.n_rad, nz = M.nz;
+    const int ri0 = p.ri, zj0 = p.zj;
+    // test_exit_grid_cyl and the star's cell, as in fly_step_2d (bitwise, no short-circuit)
+    const bool out = (ri0 == n_rad + 1) | ((zj0 == nz + 1) & (fabs(p.z) > M.zmaxmax));
+    // (a cell's key is >= 0, so it equals no packet's star_key = -1: neither that test nor a wave-uniform one is needed.
+    // This rests on the cylindrical grids' encoding, "no star" = -1 (flight_clear, the star's key in the emission); the
+    // Voronoi walk's "none" is 0 and has its own test)
+    const bool killed = (ri0 + (n_rad + 2) * (zj0 + nz + 1) == p.star_key);
+    const bool leave = out | killed;
+    if (__builtin_expect(leave, 0)) {  // (once per packet)
+      p.st = out ? S_EXITED : S_EMIT;
+    } else {
+      const int ic = p.ic;
+      const bool dep = (ic < M.n_cells) && !MCGPU_DIAG(A.flags, 1);  // (p.ic = n_cells: "no cell")
+      const double x0 = p.x, y0 = p.y, z0 = p.z, u = p.u, v = p.v, w = p.w;
+      double l, z1;
+      int ri1, zj1;
+      fly_geom_2d(T, M, p, l, z1, ri1, zj1);
+      // 4) optical depth of the crossing, stop or go on (kf was loaded at the end of the previous crossing)
+      const double tau = l * (p.kap * p.kf);
+      if (__builtin_expect(tau > p.extr, 0)) {  // the stop (once per flight): the whole commit of the stopping point
+        const double lc = l * (p.extr / tau);
+        if (dep) deposit<LDSE>(A.E_abs, E_lds, ic, p.kab * lc * p.S0);
+        p.x = __builtin_fma(lc, u, x0);
+        p.y = __builtin_fma(lc, v, y0);
+        p.z = __builtin_fma(lc, w, z0);
+        p.extr = p.extr - tau;
+        p.pk_cross += 1u;
+        p.st = S_INTERACT;
+      } else {
+        if (dep) deposit<LDSE>(A.E_abs, E_lds, ic, p.kab * l * p.S0);  // save_radiation_field
+        const bool next_real = ((unsigned)(ri1 - 1) < (unsigned)n_rad) & ((unsigned)(zj1 - 1) < (unsigned)nz);
+        const int ic1 = next_real ? (ri1 - 1) + n_rad * (zj1 - 1) : M.n_cells;  // (n_cells: the entry of "no cell", 0)
+        p.extr = p.extr - tau;
+        p.pk_cross += 1u;
+        if (MRW) p.pk_cross |= 0x80000000u;  // (this flight has left the cell it started in)
+        bool mirror = false;
+        if (DARK) mirror = next_real && M.dark[next_real ? ic1 : 0];
+        if (DARK && mirror) {  // back at the entry point of this cell, an interaction follows there
+          // (the point as fly_step_2d forms it for a packet that stays: x0 + 0 u)
+          p.x = __builtin_fma(0.0, u, x0); p.y = __builtin_fma(0.0, v, y0); p.z = __builtin_fma(0.0, w, z0);
+          p.u = -u; p.v = -v; p.w = -w;
+          c_dark += 1u;
+          p.st = S_INTERACT;
+        } else {
+          const double2 kk1 = VAR ? M.v_kk[(size_t)ic1 * M.n_lambda + (p.lam - 1)] : make_double2(M.kappa_factor[ic1], 0.0);
+          p.x = __builtin_fma(l, u, x0);
+          p.y = __builtin_fma(l, v, y0);
+          p.z = z1;
+          p.ri = ri1; p.zj = zj1; p.ic = ic1;
+          p.kf = kk1.x;
+          if (VAR) p.kab = kk1.y;
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // The 2D crossing parametrised along the flight (round 5; option "crossing" = 1, OFF by default).
 // Along one straight flight the point is r(s) = r0 + s d, and everything the crossing recomputes from the current point
 // -- r^2, r.d, the discriminants of both circles -- is a function of constants of the flight: with b0 = (x0 u + y0 v) / a
@@ -1035,13 +1185,16 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         FlightParam FP;
         unsigned int c_cross_wave = 0u;
         bool any_star = true;
-        if (PARAM || (!VORO && !L3D)) any_star = __ballot(st == S_FLIGHT && F.star_key >= 0) != 0ull;
+        if (PARAM) any_star = __ballot(st == S_FLIGHT && F.star_key >= 0) != 0ull;
         if (PARAM) param_begin(F, FP);
         const bool flew = (st == S_FLIGHT);
+        constexpr bool VISIT = !PARAM && !VORO && !L3D;  // fly_visit_step_2d: the flight predicate is carried, F.st follows
+        // (VISIT: every lane counts its own crossings, once per visit: what its packet's counter gained; bit 31 is the walk's)
+        if (VISIT) c_cross -= F.pk_cross & 0x7FFFFFFFu;
 #pragma unroll 1
         for (int it = 0; it < fly_iters; ++it) {
           // back to the rings as soon as enough lanes have nothing to fly (or after fly_iters crossings)
-          if (it > 0 && __popcll(__ballot(F.st != S_FLIGHT)) >= fly_idle) break;
+          if (!VISIT && it > 0 && __popcll(__ballot(F.st != S_FLIGHT)) >= fly_idle) break;
           RQ_DIAG(if (lane == 0) d_fly_iters++; if (F.st == S_FLIGHT) d_fly_cross++;)
           if (PARAM) {
             finished += fly_step_2d_param<LDSE>(T, M, A, E_lds, F, FP, c_cross_wave, c_kill, any_star);
@@ -1054,14 +1207,16 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
             else finished += fly_step_3d<DARK, LDSE, BIN, VAR, true, MRW>(T, M, A, E_lds, F, c_cross, c_kill, c_dark, dep_ic, dep_v);
             if (BIN) bin_deposit(BS, A.bin, A.E_abs, lane, BP, dep_ic >= 0, dep_ic, dep_v);
           } else {
-            finished += fly_step_2d<DARK, LDSE, MRW, false, VAR, true>(T, M, A, E_lds, F, c_cross_wave, c_kill, c_dark, nullptr, nullptr, any_star);
+            fly_visit_step_2d<DARK, LDSE, MRW, VAR>(T, M, A, E_lds, F, c_dark);
+            if (__popcll(__ballot(F.st != S_FLIGHT)) >= fly_idle) break;  // (the same vote, taken behind the crossing)
           }
         }
         if (BIN) bin_settle(BS, A.bin, A.E_abs, lane, BP);
         if (PARAM) param_end(F, FP);
         if (PARAM || (!VORO && !L3D)) {
-          if (lane == 0) c_cross += c_cross_wave;
-          if (!PARAM && flew && F.st == S_EMIT) { c_kill++; finished += 1; }  // killed at the star's cell (fly_step_2d WAVE)
+          if (VISIT) c_cross += F.pk_cross & 0x7FFFFFFFu;
+          else if (lane == 0) c_cross += c_cross_wave;
+          if (!PARAM && flew && F.st == S_EMIT) { c_kill++; finished += 1; }  // killed at the star's cell (fly_visit_step_2d)
           // a packet that never leaves: flag it, drop it (once per visit; MRW: bit 31 is the walk's, see fly_step_2d)
           if ((MRW && !PARAM ? (F.pk_cross & 0x7FFFFFFFu) : F.pk_cross) > 200000000u && F.st == S_FLIGHT) { *A.err = 13; F.st = S_EMIT; finished += 1; }
         }

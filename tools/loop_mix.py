@@ -5,9 +5,12 @@
 Compiles mcfost_amd/csrc/kern_roles.hip (and kern_tail.hip, for the register report) with the library's flags plus
 --cuda-device-only -S into a temporary directory, cuts out the function of one instantiation (default: the Pascucci
 headline's k_thermal_roles<false,false,false,true,false>) and finds its flying loop: the innermost natural loop whose body
-holds the LDS deposit (ds_add_f64).  The loop's blocks are split into the common path and the rare blocks -- those that
-hold the stop's division (v_div_scale_f64), the default-real zj fallback (v_cvt_f32_f64) or the runaway store
-(global_store) -- and each part is counted by kind.  Both sides of a divergent if/else count: a wave runs both.
+holds the LDS deposit (ds_add_f64).  The loop's blocks are split into the common path and the rare blocks, and each part
+is counted by kind.  Rare are the blocks that hold the stop's division (v_div_scale_f64), the default-real zj fallback
+(v_cvt_f32_f64) or the runaway store (global_store), and every block that one of these dominates, unless it also
+dominates the loop's latch (a region without a skip branch is part of the straight line): the stop's own deposit and
+commit sit in blocks of their own behind its division, while the deposit of the lanes that go on is in the common path.
+Both sides of a divergent if/else count: a wave runs both.
 
 What the counts mean:
   VALU        every v_* instruction (v_readlane / v_writelane included)
@@ -141,7 +144,7 @@ def natural_loops(n, succ):
                             body.add(p)
                             stack.append(p)
                 loops.append((h, body))
-    return loops
+    return loops, dom
 
 
 def mix(lines):
@@ -175,7 +178,7 @@ def mix(lines):
 
 def flying_loop(body, which=0):
     blocks, succ = basic_blocks(body)
-    loops = natural_loops(len(blocks), succ)
+    loops, dom = natural_loops(len(blocks), succ)
     dep_blocks = [i for i, (s, e) in enumerate(blocks) if any(re.match(r"^\s+ds_add_f64\b", body[k]) for k in range(s, e))]
     if not dep_blocks:
         raise SystemExit("no LDS deposit (ds_add_f64) in this function")
@@ -186,11 +189,14 @@ def flying_loop(body, which=0):
             found.append(cands[0])
     found.sort(key=lambda l: blocks[l[0]][0])
     h, loop = found[which]
+    has = lambda i, mk: any(mk in l for l in body[blocks[i][0]:blocks[i][1]])
+    latches = [t for t in loop if h in succ[t]]
+    marked = {i for i in loop if any(has(i, mk) for mk in RARE_MARKERS)}
+    side = {i for i in marked if not any(i in dom[t] for t in latches)}   # (these take what they dominate with them)
     common, rare = [], []
     for i in sorted(loop):
         s, e = blocks[i]
-        text = body[s:e]
-        (rare if any(mk in l for l in text for mk in RARE_MARKERS) else common).extend(text)
+        (rare if i in marked or any(j in dom[i] for j in side) else common).extend(body[s:e])
     return common, rare, len(found), body[blocks[h][0]].split(":")[0]
 
 
