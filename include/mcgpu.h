@@ -222,6 +222,11 @@ int mcgpu_set_midplane_snap(mcgpu_ctx *ctx, int on);
  *                      2 = the role schedule wherever it is built (also Voronoi grids);
  *                      3 = Voronoi grids: the pool schedule (packet records in HBM, queues by phase and
  *                      by neighbour-list length in LDS, one phase per wave pass; mc_voronoi_pool.hip.h)
+ *   "cell_key"     2D role kernels with the absorbed energy in LDS: how a flight names its cell.  0 (default) =
+ *                      automatic: the padded key K = ri + (n_rad + 2) zj (one name for the star test, the opacity
+ *                      and the deposit; the private grid gains a halo) unless the disk's midplane is optically
+ *                      thick, where the records that the halo displaces matter more; 1 = padded; 2 = plain.
+ *                      The same packets and deposits either way.
  *   "crossing"     0 (default) = the reference's crossing arithmetic everywhere (cross_cylindrical_cell,
  *                      cylindrical_grid.f90:918-1175: golden walks bit for bit, packets equal to the CPU
  *                      restatement's one for one); 1 = 2D grids without dark zone / random walk / dust

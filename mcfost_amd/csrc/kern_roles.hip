@@ -8,7 +8,11 @@
 
 namespace mcgpu {
 
-const void* kpick_roles(bool l3d, bool pola, bool dark, bool lds, bool mrw) {
+const void* kpick_roles(bool l3d, bool pola, bool dark, bool lds, bool mrw, bool pad) {
+  if (pad && !l3d && lds)   // the padded cell key: 2D grids with LDS deposits
+    return bsel(pola, [&](auto POLA) { return bsel(dark, [&](auto DARK) { return bsel(mrw, [&](auto MRW) -> const void* {
+      return (const void*)k_thermal_roles<false, MCGPU_BV(POLA), MCGPU_BV(DARK), true, MCGPU_BV(MRW), true>;
+    }); }); });
   return bsel(l3d, [&](auto L3D) { return bsel(pola, [&](auto POLA) { return bsel(dark, [&](auto DARK) { return bsel(lds, [&](auto LDSE) {
     return bsel(mrw, [&](auto MRW) -> const void* {
       if constexpr (MCGPU_BV(L3D) && MCGPU_BV(MRW)) return nullptr;   // (the role schedule's walk is 2D)

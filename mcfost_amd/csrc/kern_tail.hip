@@ -12,7 +12,11 @@
 
 namespace mcgpu {
 
-const void* kpick_roles_tail(bool pola, bool dark, bool lds, bool mrw) {
+const void* kpick_roles_tail(bool pola, bool dark, bool lds, bool mrw, bool pad) {
+  if (pad && lds)   // the padded cell key: LDS deposits
+    return bsel(pola, [&](auto POLA) { return bsel(dark, [&](auto DARK) { return bsel(mrw, [&](auto MRW) -> const void* {
+      return (const void*)k_thermal_roles_tail<MCGPU_BV(POLA), MCGPU_BV(DARK), true, MCGPU_BV(MRW), true>;
+    }); }); });
   return bsel(pola, [&](auto POLA) { return bsel(dark, [&](auto DARK) { return bsel(lds, [&](auto LDSE) {
     return bsel(mrw, [&](auto MRW) -> const void* {
       return (const void*)k_thermal_roles_tail<MCGPU_BV(POLA), MCGPU_BV(DARK), MCGPU_BV(LDSE), MCGPU_BV(MRW)>;

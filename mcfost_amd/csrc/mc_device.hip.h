@@ -52,6 +52,22 @@ constexpr float FLT_TINY = 1.17549435082228750797e-38f;
 constexpr float FLT_HUGE = 3.40282346638528859812e+38f;
 constexpr float FLT_TINY_X1E6 = 1.17549435082228750797e-38f * 1.0e6f;  // tiny_real_x1e6 (constants.f90:156)
 
+// The Newton sequence of sqrt_nonneg (below) from its seed y ~ 1 / sqrt(x): v_rsq_f64 on the device; tests/emu, which has
+// no such instruction, hands in a seed of its own and so runs this very code.
+__device__ __forceinline__ double sqrt_nonneg_from_seed(double x, double y) {
+  double g = x * y;
+  double h = y * 0.5;
+  const double r = __builtin_fma(-h, g, 0.5);
+  g = __builtin_fma(g, r, g);
+  h = __builtin_fma(h, r, h);
+  double d = __builtin_fma(-g, g, x);
+  g = __builtin_fma(d, h, g);
+  d = __builtin_fma(-g, g, x);
+  g = __builtin_fma(d, h, g);
+  // x = 0: y is infinite and g = 0 * inf a NaN, of which the maximum makes the 0 that is wanted; x > 0: g >= 0 as it is
+  return __builtin_fmax(g, 0.0);
+}
+
 // Products and sums that must NOT be contracted into FMA (hipcc's default -ffp-contract=
 // fast-honor-pragmas fuses a*b+c everywhere else, and HIP's __fmul_rn/nd_add are plain
 // operators that get fused too): used where the reference's unfused default-real / FP64
@@ -81,20 +97,20 @@ __device__ __forceinline__ double nd_add(double a, double b) {
 // into -- v_rsq_f64 and two coupled Newton steps -- without the rescaling of tiny arguments and the infinity test
 // that sequence carries for the general case (7 of its 24 vector instructions).  The same bits as sqrt() on that
 // domain; the crossing's discriminants (AU^2) are never anywhere near 1e-231.
-__device__ __forceinline__ double sqrt_nonneg(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  double g = x * y;
-  double h = y * 0.5;
-  const double r = __builtin_fma(-h, g, 0.5);
-  g = __builtin_fma(g, r, g);
-  h = __builtin_fma(h, r, h);
-  double d = __builtin_fma(-g, g, x);
-  g = __builtin_fma(d, h, g);
-  d = __builtin_fma(-g, g, x);
-  g = __builtin_fma(d, h, g);
-  return (x == 0.0) ? 0.0 : g;
-}
+__device__ __forceinline__ double sqrt_nonneg(double x) { return sqrt_nonneg_from_seed(x, __builtin_amdgcn_rsq(x)); }
 #endif
+// (int)x for x >= 0 that may be far beyond the integers: v_cvt_i32_f64 saturates and gives 0 for a NaN.  The C++ cast is
+// undefined there and there is no __builtin_amdgcn_ for this conversion, so the instruction is named (one instruction, no
+// side effects: the compiler may still move it); the host emulation writes the same answers out.
+__device__ __forceinline__ int f64_to_i32_sat(double x) {
+#ifdef MCGPU_LANE_EMULATION
+  return x >= 2147483647.0 ? 2147483647 : (x == x ? (int)x : 0);
+#else
+  int r;
+  asm("v_cvt_i32_f64 %0, %1" : "=v"(r) : "v"(x));
+  return r;
+#endif
+}
 // ... without the last correction step: within a few units in the last place (the flight-parametric crossing, which
 // makes no claim on the reference's last bits)
 __device__ __forceinline__ double sqrt_fast_nonneg(double x) {
@@ -174,8 +190,10 @@ struct DevModel {
   const double* kappa;
   const double* kappa_abs;
   const float* albedo;
-  const double* kappa_factor;  // [n_cells]
-  const unsigned char* dark;   // [n_cells] or null
+  // (2D cylindrical grids: each table is followed by its copy in the padded layout of mc_roles.hip.h (pad_cells_2d values,
+  // the halo 0), for the role kernels that name a cell by its padded key)
+  const double* kappa_factor;  // [n_cells], then one 0 for "no cell" [, then the padded copy]
+  const unsigned char* dark;   // [n_cells] [, then the padded copy] or null
   // scattering
   int nang, aniso_method, lisotropic, p_lambda_fixed;
   const float* prob_s11;  // (0:nang, n_lambda)

@@ -16,12 +16,12 @@ const void* kpick_thermal_sph(bool l3d, bool pola, bool lds, bool mrw);
 // kern_sph_ext.hip: the spherical grid with a dark zone and / or dust classes -- k_thermal_sph_ext (no random walk)
 const void* kpick_thermal_sph_ext(bool l3d, bool pola, bool dark, bool lds, bool var);
 // kern_roles.hip: waves with roles -- k_thermal_roles (mrw: 2D only)
-const void* kpick_roles(bool l3d, bool pola, bool dark, bool lds, bool mrw);
+const void* kpick_roles(bool l3d, bool pola, bool dark, bool lds, bool mrw, bool pad);
 // ... k_thermal_roles_param: 2D, LDS deposits, the flight-parametric crossing in the flying waves (option "crossing" = 1)
 const void* kpick_roles_param(bool pola, bool tail);
 // kern_tail.hip: the kernels of a launch's end -- k_thermal_roles_tail (2D, hands packets over), k_thermal_roles_bin
 // (3D, binned deposits, chunks), k_tail (one packet per wave)
-const void* kpick_roles_tail(bool pola, bool dark, bool lds, bool mrw);
+const void* kpick_roles_tail(bool pola, bool dark, bool lds, bool mrw, bool pad);
 const void* kpick_roles_bin(bool pola, bool dark, bool mrw);
 const void* kpick_tail(bool l3d, bool pola, bool dark, bool mrw);
 // kern_var.hip / kern_var_single.hip: lvariable_dust -- k_thermal_roles_var, k_thermal_var

@@ -169,8 +169,50 @@ struct Flight {
   int ri, zj, k, star_key, st;
   unsigned int pk_cross;
   int lam;  // (VAR: the packet's wavelength, for the per-cell opacities)
-  int ic;   // (2D crossing: the 0-based index of the cell (ri, zj), n_cells outside the real cells; flight_constants sets it)
+  int ic;   // (2D crossing: the 0-based index of the cell (ri, zj), n_cells outside the real cells; flight_constants sets it.
+            // PAD: the padded key of (ri, zj), see below)
 };
+
+// PAD: one name for a cell of a 2D grid.  The crossing names the cell (ri, zj) three ways -- the key of the star's cell, the
+// index of its kappa_factor and the slot of its deposit -- and two of them need a "no cell" for the hole (ri = 0), the
+// layer above the disk (zj = nz + 1) and the outside (ri = n_rad + 1).  The padded key K = ri + (n_rad + 2) zj over
+// 0 <= ri <= n_rad + 1, 0 <= zj <= nz + 1 is all three: the opacities have a copy in that layout whose halo is 0 (behind
+// the plain table, see DevModel::kappa_factor), the workgroup's absorbed-energy grid in LDS is laid out the same way -- its
+// halo slots take the deposits of the virtual cells and are never folded -- and a star's key is this one plus a constant
+// (pad_star_bias), taken off for the time a flight spends in a crossing loop.  The role kernels of 2D grids with LDS deposits and one
+// dust class carry K in Flight::ic; everything else keeps the plain index (PAD = false is the specification).
+__host__ __device__ inline int pad_cells_2d(int n_rad, int nz) { return (n_rad + 2) * (nz + 2); }
+__host__ __device__ inline int pad_key_2d(int n_rad, int ri, int zj) { return ri + (n_rad + 2) * zj; }
+__host__ __device__ inline int pad_star_bias(int n_rad, int nz) { return (n_rad + 2) * (nz + 1); }
+// the 0-based index of the real cell behind a padded key, -1 in the halo (the host's padded tables, the tests)
+__host__ __device__ inline int pad_cell_of_key(int n_rad, int nz, int K) {
+  const int zj = K / (n_rad + 2), ri = K - zj * (n_rad + 2);
+  return (ri >= 1 && ri <= n_rad && zj >= 1 && zj <= nz) ? (ri - 1) + n_rad * (zj - 1) : -1;
+}
+// The folds of a padded private grid go by rows, so that no slot has to be divided back into (ri, zj): slice `slice` of
+// n_slices takes the rows zj = 1 + slice, 1 + slice + n_slices, ... <= nz, a lane of it the cells ri = 1 + lane, 65 + lane,
+// ... <= n_rad; fn(K, ic) gets the padded key and the 0-based index of each.  All slices together: every real cell once,
+// no halo slot ever.
+template <typename Fn>
+__device__ inline void pad_fold_rows(int n_rad, int nz, int n_slices, int slice, int lane, Fn&& fn) {
+  for (int zj = 1 + slice; zj <= nz; zj += n_slices)
+    for (int ri = 1 + lane; ri <= n_rad; ri += 64) fn(pad_key_2d(n_rad, ri, zj), (ri - 1) + n_rad * (zj - 1));
+}
+// the padded copy of a per-cell table of a 2D grid (n_rad * nz values -> pad_cells_2d values, the halo 0)
+template <typename Tp>
+inline void pad_table_2d(int n_rad, int nz, const Tp* plain, Tp* padded) {
+  for (int K = 0; K < pad_cells_2d(n_rad, nz); ++K) {
+    const int ic = pad_cell_of_key(n_rad, nz, K);
+    padded[K] = ic >= 0 ? plain[ic] : Tp(0);
+  }
+}
+// where the padded copies lie: behind the plain tables' entries (n_cells + 1 factors, n_cells flags), in the same arrays
+__device__ __forceinline__ const double* pad_kappa_factor(const DevModel& M) { return M.kappa_factor + (M.n_cells + 1); }
+__device__ __forceinline__ const unsigned char* pad_dark(const DevModel& M) { return M.dark + M.n_cells; }
+// entry K of the padded factors: a 32-bit byte offset on the (wave-uniform) base
+__device__ __forceinline__ double pad_load_kf(const double* kf_pad, int K) {
+  return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(kf_pad) + ((unsigned int)K << 3));
+}
 
 __device__ inline void flight_clear(Flight& F) {
   F.x = F.y = F.z = F.u = F.v = 0.0; F.w = 1.0; F.extr = 0.0; F.S0 = 1.0; F.inv_a = F.inv_w = F.kf = F.kap = F.kab = 0.0;
@@ -188,11 +230,21 @@ __device__ inline void var_cell_opacities(const DevModel& M, Flight& F, int ic) 
 
 // REUSE (the tail kernel, whose trapped packets start flight after flight in one cell): F.ic / F.kf still hold the last
 // flight's cell and its kappa_factor (F.ic = -1: nothing yet), and the load from HBM is skipped while the cell is the same
-template <bool L3D, bool VAR = false, bool REUSE = false>
+// PAD: F.ic is the padded key and the factor comes from the padded table (indices that name no slot: slot 0, a halo)
+template <bool L3D, bool VAR = false, bool REUSE = false, bool PAD = false>
 __device__ inline void flight_constants(const Lds& T, const DevModel& M, Flight& F, int lambda) {
+  static_assert(!PAD || (!L3D && !VAR && !REUSE), "the padded key: 2D grids, one dust class, the role kernels");
   const double a = F.u * F.u + F.v * F.v;  // cylindrical_grid.f90:941-952
   F.inv_a = (a > TINY_REAL) ? 1.0 / a : HUGE_REAL;
   F.inv_w = (fabs(F.w) > TINY_REAL) ? 1.0 / F.w : copysign(HUGE_DP, F.w);
+  if (PAD) {
+    const bool in_pad = ((unsigned)F.ri <= (unsigned)(M.n_rad + 1)) & ((unsigned)F.zj <= (unsigned)(M.nz + 1));
+    F.ic = in_pad ? pad_key_2d(M.n_rad, F.ri, F.zj) : 0;
+    F.kap = T.kappa[lambda - 1];
+    F.kab = T.kabs[lambda - 1];
+    F.kf = pad_kappa_factor(M)[F.ic];
+    return;
+  }
   const int ic_new = is_real_cell<L3D>(M.n_rad, M.nz, F.ri, F.zj) ? cell_index<L3D>(M.n_rad, M.nz, F.ri, F.zj, F.k) : M.n_cells;
   if (REUSE && !VAR && ic_new == F.ic) {
     F.kap = T.kappa[lambda - 1];
@@ -290,10 +342,13 @@ __device__ inline int roles_cross(const Lds& T, const DevModel& M, const RunArgs
 // counter), the star's cell is tested only when any_star says some lane of the wave flies towards one, and the caller
 // counts the packets killed there and tests the packet's crossing counter for a runaway, once per visit.  Positions,
 // indices, deposits: the same bits.
-template <bool DARK, bool LDSE, bool MRW = false, bool OUT = false, bool VAR = false, bool WAVE = false>
+// PAD: p.ic is the padded key, p.star_key the star's cell in that key, the deposit goes to the padded grid (see Flight).
+// PAD = false is the specification of that form (tests/emu/emu_fly_pad.cpp walks both).
+template <bool DARK, bool LDSE, bool MRW = false, bool OUT = false, bool VAR = false, bool WAVE = false, bool PAD = false>
 __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, const RunArgs& A, double* E_lds, Flight& p,
                                            unsigned int& c_cross, unsigned int& c_kill, unsigned int& c_dark,
                                            int* dep_ic = nullptr, double* dep_v = nullptr, bool any_star = true) {
+  static_assert(!PAD || (LDSE && !OUT && !VAR), "the padded key: LDS deposits, one dust class");
   const int n_rad = M.n_rad, nz = M.nz;
   // correct_plus = 1 + e and correct_moins = 1 - e with e = 45 * 2^-52 EXACTLY (1e-14 rounds to 45 units in the last
   // place of 1.0 and 90 of the doubles below it): a * correct_plus = a + a e is then one fma(a, e, a) -- the very
@@ -308,13 +363,14 @@ __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, cons
   // (bitwise: compares and mask operations, no short-circuit)
   const bool out = (ri0 == n_rad + 1) | (top & (fabs(z0) > M.zmaxmax));
   bool killed = false;
-  if (!WAVE || any_star) killed = (p.star_key >= 0) & (ri0 + (n_rad + 2) * (zj0 + nz + 1) == p.star_key);
+  if (PAD) killed = (p.ic == p.star_key);  // (a key is >= 0, "no star" below 0)
+  else if (!WAVE || any_star) killed = (p.star_key >= 0) & (ri0 + (n_rad + 2) * (zj0 + nz + 1) == p.star_key);
   const bool go = active && !out && !killed;
   const bool hole = (ri0 == 0);
   // the cell's index travels with the flight (p.ic; n_cells = "no cell"): what the last crossing computed for the
   // kappa_factor of this cell is the address of this crossing's deposit
   const int ic = p.ic;
-  const bool real_cell = ic < M.n_cells;
+  const bool real_cell = PAD || ic < M.n_cells;  // (PAD: every cell has a slot)
   // the row of this radial index (lanes outside the grid read a valid row; their results are discarded)
   const RowT& R0 = T.row[ri0];
 
@@ -398,13 +454,17 @@ __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, cons
 
   // the next cell; DARK: mirrored back at the wall of a dark cell (see roles_cross)
   // (unsigned compares: 1 <= ri1 <= n_rad and 1 <= zj1 <= nz in one test each)
-  const bool next_real = ((unsigned)(ri1 - 1) < (unsigned)n_rad) & ((unsigned)(zj1 - 1) < (unsigned)nz);
-  const int ic1 = next_real ? (ri1 - 1) + n_rad * (zj1 - 1) : M.n_cells;  // (n_cells: the entry of "no cell", 0)
+  const bool next_real = PAD || (((unsigned)(ri1 - 1) < (unsigned)n_rad) & ((unsigned)(zj1 - 1) < (unsigned)nz));
+  // (PAD: every lane computes here, also one that has left through the outer edge, ri0 = n_rad + 1, whose "next" radial
+  // index lies past the padding: it names the last column, a halo, so that the load below stays inside the table)
+  const int ic1 = PAD ? pad_key_2d(n_rad, ri1 > n_rad + 1 ? n_rad + 1 : ri1, zj1)
+                      : (next_real ? (ri1 - 1) + n_rad * (zj1 - 1) : M.n_cells);  // (n_cells: the entry of "no cell", 0)
   bool mirror = false;
-  if (DARK) mirror = go && !stop && next_real && M.dark[next_real ? ic1 : 0];
+  if (DARK) mirror = go && !stop && next_real && (PAD ? pad_dark(M)[ic1] : M.dark[next_real ? ic1 : 0]);
   const bool move = go && !stop && !mirror;
   // (VAR: the pair (kappa kappa_factor, kappa_abs_LTE) of the next cell and this wavelength, see var_cell_opacities)
-  const double2 kk1 = VAR ? M.v_kk[(size_t)ic1 * M.n_lambda + (p.lam - 1)] : make_double2(M.kappa_factor[ic1], 0.0);
+  const double2 kk1 = VAR ? M.v_kk[(size_t)ic1 * M.n_lambda + (p.lam - 1)]
+                          : make_double2(PAD ? pad_load_kf(pad_kappa_factor(M), ic1) : M.kappa_factor[ic1], 0.0);
   const double kf1 = kk1.x;
 
   // 5) commit
@@ -516,7 +576,10 @@ __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, cons
   const int ri1 = rad ? ri0 + delta_rad : ri0;
   const double qd = fabs(z1) * T.row[ri1].rzn;
   const double fl = floor(qd);
-  int zjr = (int)fmin(fl, (double)nz) + 1;
+  // (the minimum on the integers, behind a conversion that saturates: for fl >= 0 the same zj as fly_step_2d's minimum on
+  // the doubles; a NaN, which only a broken state brings here, gives zj = 1 where that gives nz + 1)
+  const int fli = f64_to_i32_sat(fl);
+  int zjr = (fli < nz ? fli : nz) + 1;
   const bool rad_in = rad && (ri1 >= 1) && (ri1 <= n_rad);
   const double fr = qd - fl;
   if (__builtin_expect(rad_in && (fr < 1.0e-4 || fr > 1.0 - 1.0e-4), 0)) {  // (rare)
@@ -533,10 +596,16 @@ __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, cons
 
 // One crossing of the lanes in flight.  The caller counts the crossings (p.pk_cross), the packets killed at the star's
 // cell (p.st == S_EMIT) and tests the crossing counter for a runaway, once per visit.
-template <bool DARK, bool LDSE, bool MRW = false, bool VAR = false>
+// PAD (see Flight): p.ic is the padded key K of the cell, p.star_key the star's cell in that key; kf_pad / dark_pad are the
+// padded tables (pad_kappa_factor, pad_dark: the caller forms the addresses once).  The star test is one compare of two
+// carried registers, the deposit is unconditional, and the next cell's key is one multiply-add that is also the offset of
+// its factor -- no "no cell" anywhere.
+template <bool DARK, bool LDSE, bool MRW = false, bool VAR = false, bool PAD = false>
 __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& M, const RunArgs& A, double* E_lds, Flight& p,
-                                                  unsigned int& c_dark) {
+                                                  unsigned int& c_dark, const double* kf_pad = nullptr,
+                                                  const unsigned char* dark_pad = nullptr) {
   static_assert((1.0 + GRID_PREC) - 1.0 == 0x1.68p-47 && 1.0 - (1.0 - GRID_PREC) == 0x1.68p-47, "grid_prec is not 45 ulp");
+  static_assert(!PAD || (LDSE && !VAR), "the padded key: LDS deposits, one dust class");
   if (p.st == S_FLIGHT) {
     const int n_rad = M.n_rad, nz = M.nz;
     const int ri0 = p.ri, zj0 = p.zj;
@@ -544,38 +613,39 @@ __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& 
     const bool out = (ri0 == n_rad + 1) | ((zj0 == nz + 1) & (fabs(p.z) > M.zmaxmax));
     // (a cell's key is >= 0, so it equals no packet's star_key = -1: neither that test nor a wave-uniform one is needed.
     // This rests on the cylindrical grids' encoding, "no star" = -1 (flight_clear, the star's key in the emission); the
-    // Voronoi walk's "none" is 0 and has its own test)
-    const bool killed = (ri0 + (n_rad + 2) * (zj0 + nz + 1) == p.star_key);
+    // Voronoi walk's "none" is 0 and has its own test.  PAD: "no star" is -1 - pad_star_bias, below 0 as well)
+    const bool killed = PAD ? (p.ic == p.star_key) : (ri0 + (n_rad + 2) * (zj0 + nz + 1) == p.star_key);
     const bool leave = out | killed;
     if (__builtin_expect(leave, 0)) {  // (once per packet)
       p.st = out ? S_EXITED : S_EMIT;
     } else {
       const int ic = p.ic;
-      const bool dep = (ic < M.n_cells) && !MCGPU_DIAG(A.flags, 1);  // (p.ic = n_cells: "no cell")
+      const bool dep = (PAD || ic < M.n_cells) && !MCGPU_DIAG(A.flags, 1);  // (p.ic = n_cells: "no cell"; PAD: every cell has a slot)
       const double x0 = p.x, y0 = p.y, z0 = p.z, u = p.u, v = p.v, w = p.w;
       double l, z1;
       int ri1, zj1;
       fly_geom_2d(T, M, p, l, z1, ri1, zj1);
       // 4) optical depth of the crossing, stop or go on (kf was loaded at the end of the previous crossing)
       const double tau = l * (p.kap * p.kf);
-      if (__builtin_expect(tau > p.extr, 0)) {  // the stop (once per flight): the whole commit of the stopping point
-        const double lc = l * (p.extr / tau);
+      // (what both ways share is committed once, in front of the branch)
+      const double extr0 = p.extr;
+      p.extr = extr0 - tau;
+      p.pk_cross += 1u;
+      if (__builtin_expect(tau > extr0, 0)) {  // the stop (once per flight): the whole commit of the stopping point
+        const double lc = l * (extr0 / tau);
         if (dep) deposit<LDSE>(A.E_abs, E_lds, ic, p.kab * lc * p.S0);
         p.x = __builtin_fma(lc, u, x0);
         p.y = __builtin_fma(lc, v, y0);
         p.z = __builtin_fma(lc, w, z0);
-        p.extr = p.extr - tau;
-        p.pk_cross += 1u;
         p.st = S_INTERACT;
       } else {
         if (dep) deposit<LDSE>(A.E_abs, E_lds, ic, p.kab * l * p.S0);  // save_radiation_field
-        const bool next_real = ((unsigned)(ri1 - 1) < (unsigned)n_rad) & ((unsigned)(zj1 - 1) < (unsigned)nz);
-        const int ic1 = next_real ? (ri1 - 1) + n_rad * (zj1 - 1) : M.n_cells;  // (n_cells: the entry of "no cell", 0)
-        p.extr = p.extr - tau;
-        p.pk_cross += 1u;
+        const bool next_real = PAD || (((unsigned)(ri1 - 1) < (unsigned)n_rad) & ((unsigned)(zj1 - 1) < (unsigned)nz));
+        const int ic1 = PAD ? pad_key_2d(n_rad, ri1, zj1)
+                            : (next_real ? (ri1 - 1) + n_rad * (zj1 - 1) : M.n_cells);  // (n_cells: the entry of "no cell", 0)
         if (MRW) p.pk_cross |= 0x80000000u;  // (this flight has left the cell it started in)
         bool mirror = false;
-        if (DARK) mirror = next_real && M.dark[next_real ? ic1 : 0];
+        if (DARK) mirror = next_real && (PAD ? dark_pad[ic1] : M.dark[next_real ? ic1 : 0]);
         if (DARK && mirror) {  // back at the entry point of this cell, an interaction follows there
           // (the point as fly_step_2d forms it for a packet that stays: x0 + 0 u)
           p.x = __builtin_fma(0.0, u, x0); p.y = __builtin_fma(0.0, v, y0); p.z = __builtin_fma(0.0, w, z0);
@@ -583,7 +653,8 @@ __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& 
           c_dark += 1u;
           p.st = S_INTERACT;
         } else {
-          const double2 kk1 = VAR ? M.v_kk[(size_t)ic1 * M.n_lambda + (p.lam - 1)] : make_double2(M.kappa_factor[ic1], 0.0);
+          const double2 kk1 = VAR ? M.v_kk[(size_t)ic1 * M.n_lambda + (p.lam - 1)]
+                                  : make_double2(PAD ? pad_load_kf(kf_pad, ic1) : M.kappa_factor[ic1], 0.0);
           p.x = __builtin_fma(l, u, x0);
           p.y = __builtin_fma(l, v, y0);
           p.z = z1;
@@ -963,7 +1034,8 @@ __device__ inline int voro_roles_cross(const Lds& T, const DevModel& M, const Ru
 // VAR: lvariable_dust -- the flights read the per-cell opacities (var_cell_opacities), the interactions the tables of the
 // cell's class (class_tables); cylindrical grids, no MRW.
 template <bool L3D, bool POLA, bool DARK, bool LDSE, bool MRW = false, bool VORO = false, bool BIN = false, bool CARRY = BIN, bool VAR = false,
-          bool PARAM = false>   // PARAM: the flying waves cross with fly_step_2d_param (2D, no dark zone, no walk, one dust class)
+          bool PARAM = false,   // PARAM: the flying waves cross with fly_step_2d_param (2D, no dark zone, no walk, one dust class)
+          bool PADK = false>    // PADK: the padded cell key (see Flight) where it applies; the launcher asks for it
 __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, double* lds_base, int n_rec, int n_srv_pref,
                                            int k_short, int fly_iters, int fly_idle, int emit_qmax,
                                            const VoroGrid* Gp = nullptr, int cache_log_ns = 0) {
@@ -973,9 +1045,15 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
   static_assert(!BIN || CARRY, "the chunks of a binned run hand their packets on");
   static_assert(!CARRY || !VORO, "no carry-over on Voronoi grids");
   static_assert(!VAR || (!MRW && !VORO && !BIN && !CARRY), "variable dust: the plain role kernel on cylindrical grids");
+  // PAD: the padded cell key (see Flight) in the flights, the private grid and the opacities' gather
+  constexpr bool PAD = PADK && !L3D && LDSE && !VORO && !BIN && !VAR && !PARAM;
   double* const E_lds = lds_base;
-  const Lds T = lds_carve(lds_base + (LDSE ? M.n_cells : 0), M);
+  const int e_cells = LDSE ? (PAD ? pad_cells_2d(M.n_rad, M.nz) : M.n_cells) : 0;   // slots of the private grid
+  const Lds T = lds_carve(lds_base + e_cells, M);
   lds_stage(T, M);
+  const double* const kf_pad = PAD ? pad_kappa_factor(M) : nullptr;
+  const unsigned char* const dark_pad = (PAD && DARK) ? pad_dark(M) : nullptr;
+  const int key_bias = PAD ? pad_star_bias(M.n_rad, M.nz) : 0;   // a record's star_key = the padded key of that cell + key_bias
   DepCache DC;
   DC.log_ns = cache_log_ns;
   DC.val = lds_base + (lds_bytes(M) + 7) / 8;
@@ -983,7 +1061,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
   const size_t cache_doubles = VORO ? (((size_t)12 << cache_log_ns) + 7) / 8 : 0;
   if (VORO)
     for (int i = threadIdx.x; i < (1 << cache_log_ns); i += blockDim.x) { DC.val[i] = 0.0; DC.tag[i] = 0; }
-  double* const bin_base = lds_base + (LDSE ? M.n_cells : 0) + (lds_bytes(M) + 7) / 8 + cache_doubles;
+  double* const bin_base = lds_base + e_cells + (lds_bytes(M) + 7) / 8 + cache_doubles;
   const size_t bin_doubles = BIN ? (bin_lds_bytes(A.bin.n_buckets) + 7) / 8 : 0;
   const BinStage BS = bin_carve(bin_base, BIN ? A.bin.n_buckets : 0);
   if (BIN) bin_init(BS, A.bin.n_buckets);
@@ -992,7 +1070,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
   unsigned int* const rings = reinterpret_cast<unsigned int*>(qbase + sizeof(RqCtl));
   Rec<POLA>* const recs = reinterpret_cast<Rec<POLA>*>(qbase + sizeof(RqCtl) + 3 * RQ_CAP * sizeof(unsigned int));
   if (LDSE)
-    for (int i = threadIdx.x; i < M.n_cells; i += blockDim.x) E_lds[i] = 0.0;
+    for (int i = threadIdx.x; i < e_cells; i += blockDim.x) E_lds[i] = 0.0;
   for (int i = threadIdx.x; i < 3 * RQ_CAP; i += blockDim.x)  // every record starts on the FREE ring
     rings[i] = (i < n_rec) ? ((((unsigned int)i + 1u) << 16) | (unsigned int)i) : 0u;
   if (threadIdx.x == 0) {
@@ -1144,7 +1222,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         }
         st = S_FLIGHT;
         if (VORO) { F.kap = T.kappa[bag_lambda - 1]; F.kab = T.kabs[bag_lambda - 1]; }
-        else flight_constants<L3D, VAR>(T, M, F, bag_lambda);
+        else flight_constants<L3D, VAR, false, PAD>(T, M, F, bag_lambda);
       }
       // stopped packets that found no flight to swap with go to a free record
       {
@@ -1191,6 +1269,9 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         constexpr bool VISIT = !PARAM && !VORO && !L3D;  // fly_visit_step_2d: the flight predicate is carried, F.st follows
         // (VISIT: every lane counts its own crossings, once per visit: what its packet's counter gained; bit 31 is the walk's)
         if (VISIT) c_cross -= F.pk_cross & 0x7FFFFFFFu;
+        // (PAD: the star's cell as a padded key while the lane is in the loop, in place: once per visit, and the records and
+        // the code that moves packets between them and the registers keep the one encoding)
+        if (PAD) F.star_key -= key_bias;
 #pragma unroll 1
         for (int it = 0; it < fly_iters; ++it) {
           // back to the rings as soon as enough lanes have nothing to fly (or after fly_iters crossings)
@@ -1207,10 +1288,11 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
             else finished += fly_step_3d<DARK, LDSE, BIN, VAR, true, MRW>(T, M, A, E_lds, F, c_cross, c_kill, c_dark, dep_ic, dep_v);
             if (BIN) bin_deposit(BS, A.bin, A.E_abs, lane, BP, dep_ic >= 0, dep_ic, dep_v);
           } else {
-            fly_visit_step_2d<DARK, LDSE, MRW, VAR>(T, M, A, E_lds, F, c_dark);
+            fly_visit_step_2d<DARK, LDSE, MRW, VAR, PAD>(T, M, A, E_lds, F, c_dark, kf_pad, dark_pad);
             if (__popcll(__ballot(F.st != S_FLIGHT)) >= fly_idle) break;  // (the same vote, taken behind the crossing)
           }
         }
+        if (PAD) F.star_key += key_bias;
         if (BIN) bin_settle(BS, A.bin, A.E_abs, lane, BP);
         if (PARAM) param_end(F, FP);
         if (PARAM || (!VORO && !L3D)) {
@@ -1373,7 +1455,8 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
             if (A.frozen) E = A.E_prior[ic];
             else {
               E = __hip_atomic_load(&A.E_abs[ic], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              if (LDSE) E += E_lds[ic] * (double)gridDim.x;
+              // (PAD: the cell's slot of the private grid, from the record: not one more register across the interaction)
+              if (LDSE) E += E_lds[PAD ? pad_key_2d(n_rad, R.ri, R.zj) : ic] * (double)gridDim.x;
               if (VORO) E += DC.pending(ic + 1) * (double)gridDim.x;
               if (BIN) E *= bin_energy_scale(A);
               E *= A.qscale;
@@ -1420,6 +1503,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
           if (__builtin_expect(walk, 0)) {  // (rare: the hint keeps its registers out of the common path, +5 % with no walks)
             Rec<POLA>& R = recs[rid];
             const int ic = VORO ? R.ri - 1 : cell_index<L3D>(n_rad, nz, R.ri, R.zj, R.k);
+            const int eic = PAD ? pad_key_2d(n_rad, R.ri, R.zj) : ic;   // (a walk stays in its cell)
             double x = R.x, y = R.y, z = R.z, u = R.u, v = R.v, w = R.w;
             int lambda = R.lambda;
             bool done;
@@ -1441,13 +1525,13 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
                 if (A.frozen) E = A.E_prior[ic];
                 else {
                   E = __hip_atomic_load(&A.E_abs[ic], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                  if (LDSE) E += E_lds[ic] * (double)gridDim.x;
+                  if (LDSE) E += E_lds[eic] * (double)gridDim.x;
                   if (BIN) E = E * bin_energy_scale(A) + walk_dep;
                   E *= A.qscale;
                 }
                 return E;
               },
-              [&](double e) { if (BIN) walk_dep += e; else deposit<LDSE>(A.E_abs, E_lds, ic, e); }, c_walks, c_steps, L3D ? R.k : 1);
+              [&](double e) { if (BIN) walk_dep += e; else deposit<LDSE>(A.E_abs, E_lds, eic, e); }, c_walks, c_steps, L3D ? R.k : 1);
             if (done) { R.x = x; R.y = y; R.z = z; R.u = u; R.v = v; R.w = w; R.lambda = lambda; }
             walk_ic = ic;
           }
@@ -1484,9 +1568,9 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
           F.st = fly ? S_FLIGHT : S_EMIT;
           if (fly) {
             F.x = R.x; F.y = R.y; F.z = R.z; F.u = R.u; F.v = R.v; F.w = R.w; F.extr = R.extr; F.S0 = R.S[0];
-            F.ri = R.ri; F.zj = R.zj; F.k = R.k; F.star_key = R.star_key; F.pk_cross = R.pk_cross;
+            F.ri = R.ri; F.zj = R.zj; F.k = R.k; F.star_key = R.star_key - key_bias; F.pk_cross = R.pk_cross;
             if (VORO) { F.kap = T.kappa[R.lambda - 1]; F.kab = T.kabs[R.lambda - 1]; }
-            else flight_constants<L3D, VAR>(T, M, F, R.lambda);
+            else flight_constants<L3D, VAR, false, PAD>(T, M, F, R.lambda);
           }
           const int n_it = flying_in_place ? fly_iters : k_short;
 #pragma unroll 1
@@ -1502,7 +1586,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
               else finished += fly_step_3d<DARK, LDSE, BIN, VAR, true, MRW>(T, M, A, E_lds, F, c_cross, c_kill, c_dark, dep_ic, dep_v);
               if (BIN) bin_deposit(BS, A.bin, A.E_abs, lane, BP, dep_ic >= 0, dep_ic, dep_v);
             } else {
-              finished += fly_step_2d<DARK, LDSE, MRW, false, VAR>(T, M, A, E_lds, F, c_cross, c_kill, c_dark);
+              finished += fly_step_2d<DARK, LDSE, MRW, false, VAR, false, PAD>(T, M, A, E_lds, F, c_cross, c_kill, c_dark);
             }
           }
           if (BIN) bin_settle(BS, A.bin, A.E_abs, lane, BP);
@@ -1565,12 +1649,20 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
     if (LDSE && ((ep + 1) % A.flush_every) == 0) {  // barrier-free partial fold (see thermal_body)
       const int n_waves = (blockDim.x + 63) >> 6;
       const int slice = (wave + (ep + 1) / A.flush_every) % n_waves;
+      if (PAD) {  // (by rows; a halo slot is nobody's cell and keeps what it collected)
+        pad_fold_rows(n_rad, nz, n_waves, slice, lane, [&](int K, int ic) {
+          const unsigned long long bits = atomicExch(reinterpret_cast<unsigned long long*>(&E_lds[K]), 0ull);
+          const double e = __longlong_as_double((long long)bits);
+          if (e != 0.0) atomic_add_f64(&A.E_abs[ic], e);
+        });
+      } else {
       const int per = (M.n_cells + n_waves - 1) / n_waves;
       const int i0 = slice * per, i1 = (i0 + per < M.n_cells) ? i0 + per : M.n_cells;
       for (int i = i0 + lane; i < i1; i += 64) {
         const unsigned long long bits = atomicExch(reinterpret_cast<unsigned long long*>(&E_lds[i]), 0ull);
         const double e = __longlong_as_double((long long)bits);
         if (e != 0.0) atomic_add_f64(&A.E_abs[i], e);
+      }
       }
     }
   }
@@ -1632,7 +1724,12 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
   }
   lds_flush_sent(T, M, A.n_sent);
   if (BIN) bin_drain(BS, A.bin, A.E_abs);
-  if (LDSE) {
+  if (LDSE && PAD) {
+    pad_fold_rows(n_rad, nz, (int)(blockDim.x >> 6), wave, lane, [&](int K, int ic) {
+      const double e = E_lds[K];
+      if (e != 0.0) atomic_add_f64(&A.E_abs[ic], e);
+    });
+  } else if (LDSE) {
     for (int i = threadIdx.x; i < M.n_cells; i += blockDim.x) {
       const double e = E_lds[i];
       if (e != 0.0) atomic_add_f64(&A.E_abs[i], e);
@@ -1677,11 +1774,14 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
 #define MCGPU_ROLES_BLOCK 1024  // threads of a workgroup of this schedule: 128 VGPRs, 4 waves per SIMD
 #endif
 
-template <bool L3D, bool POLA, bool DARK, bool LDSE, bool MRW = false>
+// PADK: the padded cell key (2D, LDSE; DevModel::kappa_factor must carry the padded copy, the private grid has
+// pad_cells_2d slots); without it the kernel is the plain form, which the launcher keeps for optically thick disks
+template <bool L3D, bool POLA, bool DARK, bool LDSE, bool MRW = false, bool PADK = false>
 __global__ void __launch_bounds__(MCGPU_ROLES_BLOCK) k_thermal_roles(const DevModel M, const RunArgs A, int n_rec, int n_srv_pref,
                                                                      int k_short, int fly_iters, int fly_idle, int emit_qmax) {
   extern __shared__ double lds_raw[];
-  roles_body<L3D, POLA, DARK, LDSE, MRW>(M, A, lds_raw, n_rec, n_srv_pref, k_short, fly_iters, fly_idle, emit_qmax);
+  roles_body<L3D, POLA, DARK, LDSE, MRW, false, false, false, false, false, PADK>(M, A, lds_raw, n_rec, n_srv_pref, k_short, fly_iters,
+                                                                                  fly_idle, emit_qmax);
 }
 
 // the same, handing its last packets to the tail kernel (mc_tail.hip.h); 2D grids (the 3D kernel below has it built in)
@@ -1694,11 +1794,12 @@ __global__ void __launch_bounds__(MCGPU_ROLES_BLOCK) k_thermal_roles_var(const D
   roles_body<L3D, POLA, DARK, LDSE, false, false, false, false, true>(M, A, lds_raw, n_rec, n_srv_pref, k_short, fly_iters, fly_idle, emit_qmax);
 }
 
-template <bool POLA, bool DARK, bool LDSE, bool MRW>
+template <bool POLA, bool DARK, bool LDSE, bool MRW, bool PADK = false>
 __global__ void __launch_bounds__(MCGPU_ROLES_BLOCK) k_thermal_roles_tail(const DevModel M, const RunArgs A, int n_rec, int n_srv_pref,
                                                                           int k_short, int fly_iters, int fly_idle, int emit_qmax) {
   extern __shared__ double lds_raw[];
-  roles_body<false, POLA, DARK, LDSE, MRW, false, false, true>(M, A, lds_raw, n_rec, n_srv_pref, k_short, fly_iters, fly_idle, emit_qmax);
+  roles_body<false, POLA, DARK, LDSE, MRW, false, false, true, false, false, PADK>(M, A, lds_raw, n_rec, n_srv_pref, k_short, fly_iters,
+                                                                                   fly_idle, emit_qmax);
 }
 
 // the same with binned deposits (3D grids: the absorbed-energy array does not fit in LDS)

@@ -152,6 +152,11 @@ struct mcgpu_ctx {
   int opt_tail = -1;        // role kernels hand their last packets to the tail kernel (mc_tail.hip.h) once a workgroup has this
                             // many left; 0: never; -1 (default): automatic -- 48 where packets get trapped (see tail_threshold())
   std::vector<double> h_r_lim;     // host copy of r_lim (cylindrical grids): the optical-thickness estimate below
+  // host copies of kappa_factor and l_dark_zone as mcgpu_set_opacity got them, and the grid their padded copies on the
+  // device were laid out for (upload_cell_opacities; 0: none)
+  std::vector<double> h_kf;
+  std::vector<unsigned char> h_dark;
+  int pad_n_rad = 0, pad_nz = 0;
   double tau_midplane = -1.0;      // radial optical depth of the midplane at the most opaque wavelength (-1: unknown)
   double last_inter_pp = -1.0;     // interactions per packet of the context's last completed thermal launch (-1: none yet)
   DevArr<unsigned int> d_tail_next;     // the tail kernel's work counter
@@ -185,6 +190,7 @@ struct mcgpu_ctx {
   int opt_schedule = 0;     // 0 = automatic (waves with roles where the queues fit), 1 = single-role kernel
   int opt_speculation = 1;  // SED mode: commit most of every stream before the scout pass
   int opt_cache_log_slots = 13;  // Voronoi deposit cache: 2^13 slots = 96 KB of LDS
+  int opt_cell_key = 0;          // the 2D role kernels' cell key: 0 = automatic (padded unless the midplane is optically thick), 1 = padded, 2 = plain
   int opt_crossing = 0;          // 1: the flight-parametric 2D crossing in the role kernel's flying waves (statistical parity only)
   int opt_pool_log_rec = 12;     // Voronoi pool schedule: 2^12 packet records per workgroup (mc_voronoi_pool.hip.h)
   int opt_nlte_stats = 0;        // 1: a non-LTE launch counts the events its waves serve (mcgpu_get_info "nlte_events" / "nlte_visits")
@@ -281,6 +287,7 @@ static void bin_release(mcgpu_ctx* ctx);
 static void nlte_release(mcgpu_ctx* ctx, bool all);
 static void grid_release(mcgpu_ctx* ctx);
 static int tail_threshold(const mcgpu_ctx* ctx);
+static int upload_cell_opacities(mcgpu_ctx* ctx);
 
 #define HIPCHK(call)                                                              \
   do {                                                                            \
@@ -407,6 +414,7 @@ extern "C" int mcgpu_set_grid_cyl(mcgpu_ctx* ctx, int n_rad, int nz, int n_az, i
   ctx->h_r_lim.resize((size_t)n_rad + 1);
   for (int i = 0; i <= n_rad; ++i) ctx->h_r_lim[i] = std::sqrt(r_lim_2[i]);
   ctx->tau_midplane = -1.0; ctx->last_inter_pp = -1.0;
+  ctx->pad_n_rad = 0; ctx->pad_nz = 0;   // (the padded copies of the opacities belong to the grid they were built for)
   const int ntot2 = l3D ? (n_rad + 2) * (2 * nz + 2) * n_az : (n_rad + 2) * (nz + 2) * n_az;
   int rc = check_cell_map(ctx, n_rad, nz, n_az, l3D, cell_map, cell_map_i, cell_map_j, cell_map_k, lexit_cell);
   if (rc) return rc;
@@ -437,6 +445,8 @@ extern "C" int mcgpu_set_grid_cyl(mcgpu_ctx* ctx, int n_rad, int nz, int n_az, i
   bin_release(ctx);
   grid_release(ctx);   // (d_prob_E, xN_abs, xJ_abs were sized for the old grid)
   ctx->have_grid = true;
+  // (opacities set before this grid: their padded copies are laid out for the grid they came with)
+  if (ctx->have_opacity && ctx->h_kf.size() == (size_t)n_cells && (rc = upload_cell_opacities(ctx))) return rc;
   return MCGPU_OK;
 }
 
@@ -626,6 +636,7 @@ extern "C" int mcgpu_set_option(mcgpu_ctx* ctx, const char* name, int value) {
   }
   else if (!strcmp(name, "schedule")) { if (value < 0 || value > 3) return fail(ctx, MCGPU_ERR_ARG, "schedule: 0, 1, 2 or 3"); ctx->opt_schedule = value; }
   else if (!strcmp(name, "speculation")) ctx->opt_speculation = value ? 1 : 0;
+  else if (!strcmp(name, "cell_key")) { if (value < 0 || value > 2) return fail(ctx, MCGPU_ERR_ARG, "cell_key: 0, 1 or 2"); ctx->opt_cell_key = value; }
   else if (!strcmp(name, "crossing")) { if (value < 0 || value > 1) return fail(ctx, MCGPU_ERR_ARG, "crossing: 0 or 1"); ctx->opt_crossing = value; }
   else if (!strcmp(name, "voronoi_pool_log_records")) { if (value < 6 || value > VP_MAX_LOG_REC) return fail(ctx, MCGPU_ERR_ARG, "voronoi_pool_log_records: 6..12"); ctx->opt_pool_log_rec = value; }
   else if (!strcmp(name, "voronoi_cache_log_slots")) { if (value < 6 || value > 13) return fail(ctx, MCGPU_ERR_ARG, "voronoi_cache_log_slots: 6..13"); ctx->opt_cache_log_slots = value; }
@@ -776,6 +787,29 @@ extern "C" int mcgpu_set_stars(mcgpu_ctx* ctx, int n_stars, const double* x, con
   return MCGPU_OK;
 }
 
+// kappa_factor and the dark flags on the device, from the context's host copies: the plain tables (the factors end in one
+// 0 for "no cell": the 2D crossing reads it for the virtual cells, mc_roles.hip.h) and, on a 2D cylindrical grid, their
+// copies in the padded layout behind them (DevModel::kappa_factor).  Called when the opacities or the grid are set.
+static int upload_cell_opacities(mcgpu_ctx* ctx) {
+  DevModel& M = ctx->M;
+  const bool pad = !ctx->voro && !M.grid_sph && !M.l3D;
+  const size_t np = pad ? (size_t)pad_cells_2d(M.n_rad, M.nz) : 0;
+  int rc;
+  std::vector<double> kfp((size_t)M.n_cells + 1 + np, 0.0);
+  std::memcpy(kfp.data(), ctx->h_kf.data(), (size_t)M.n_cells * sizeof(double));
+  if (pad) pad_table_2d(M.n_rad, M.nz, ctx->h_kf.data(), kfp.data() + M.n_cells + 1);
+  if ((rc = upload(ctx, kfp.data(), kfp.size(), &M.kappa_factor))) return rc;
+  M.dark = nullptr;
+  if (!ctx->h_dark.empty()) {
+    std::vector<unsigned char> dk((size_t)M.n_cells + np, 0);
+    std::memcpy(dk.data(), ctx->h_dark.data(), (size_t)M.n_cells);
+    if (pad) pad_table_2d(M.n_rad, M.nz, ctx->h_dark.data(), dk.data() + M.n_cells);
+    if ((rc = upload(ctx, dk.data(), dk.size(), &M.dark))) return rc;
+  }
+  ctx->pad_n_rad = pad ? M.n_rad : 0; ctx->pad_nz = pad ? M.nz : 0;
+  return MCGPU_OK;
+}
+
 extern "C" int mcgpu_set_opacity(mcgpu_ctx* ctx, int n_lambda, const double* kappa, const double* kappa_abs_LTE,
                                  const float* tab_albedo_pos, const double* kappa_factor,
                                  const unsigned char* l_dark_zone) {
@@ -802,19 +836,16 @@ extern "C" int mcgpu_set_opacity(mcgpu_ctx* ctx, int n_lambda, const double* kap
     }
     ctx->tau_midplane = tau;
   }
-  {  // one extra entry, 0: the factor of "no cell" (the 2D crossing reads it for the virtual cells, mc_roles.hip.h)
-    std::vector<double> kfp((size_t)M.n_cells + 1, 0.0);
-    std::memcpy(kfp.data(), kappa_factor, (size_t)M.n_cells * sizeof(double));
-    if ((rc = upload(ctx, kfp.data(), kfp.size(), &M.kappa_factor))) return rc;
-  }
-  M.dark = nullptr;
+  ctx->h_kf.assign(kappa_factor, kappa_factor + M.n_cells);
+  ctx->h_dark.clear();
   if (l_dark_zone) {
     bool any = false;
     for (int i = 0; i < M.n_cells; ++i) any |= (l_dark_zone[i] != 0);
     if (any && ctx->voro)  // the reference never builds a dark zone there (dust_transfer.f90:290-293)
       return fail(ctx, MCGPU_ERR_UNSUPPORTED, "no dark zone on a Voronoi grid");
-    if (any && (rc = upload(ctx, l_dark_zone, (size_t)M.n_cells, &M.dark))) return rc;
+    if (any) ctx->h_dark.assign(l_dark_zone, l_dark_zone + M.n_cells);
   }
+  if ((rc = upload_cell_opacities(ctx))) return rc;
   if (ctx->voro) {  // the cell records carry the opacity factor
     for (int i = 0; i < M.n_cells; ++i) ctx->h_cells[i].kf = kappa_factor[i];
     HIPCHK(hipMemcpy(ctx->d_cells, ctx->h_cells.data(), ctx->h_cells.size() * sizeof(VoroCell), hipMemcpyHostToDevice));
@@ -1671,11 +1702,28 @@ static int launch_mega(mcgpu_ctx* ctx, const RunArgs& A, bool use_lds, int grid_
   {
     const int rthreads = (block_threads > 0 && block_threads <= MCGPU_ROLES_BLOCK) ? block_threads : MCGPU_ROLES_BLOCK;
     if (rthreads % 64) return fail(ctx, MCGPU_ERR_ARG, "block_threads must be a multiple of 64");
-    const size_t lds_t = (lds_k + 7) / 8 * 8;
+    // the 2D role kernels with LDS deposits keep their private grid in the padded layout (mc_roles.hip.h, PAD; not the
+    // flight-parametric form): pad_cells_2d slots instead of n_cells
+    const bool param = ctx->opt_crossing == 1 && !l3d && !dark && use_lds && !M.mrw;
+    // Automatic: the padded key unless the disk's midplane is optically thick (the test that picks fly_iters below).
+    // Measured on ref4.1 2D, a thick disk: 3.3 % slower with the padded kernels, which hold 20 fewer records per workgroup
+    // and 8 B more scratch (profiles/r06_fly_pad_ab.log; which of the two costs the time is not measured).
+    // The plain kernels also serve where the padded copies were laid out for another grid, and where the larger private
+    // grid would leave no room for the records.
+    bool pad = !l3d && use_lds && !param &&
+               (ctx->opt_cell_key == 1 || (ctx->opt_cell_key == 0 && !(ctx->tau_midplane > 1000.0))) &&
+               ctx->pad_n_rad == M.n_rad && ctx->pad_nz == M.nz;
     // (the kernels that hand packets over hold 256 bytes of static LDS: a request of the full 160 KB is refused there)
     const int tail_thr = tail_threshold(ctx);
     const size_t lds_cap_r = lds_cap - ((!l3d && tail_thr > 0) ? 512 : 0);
-    int n_rec = lds_t < lds_cap_r ? rq_records_that_fit(pola, lds_cap_r - lds_t) : 0;
+    size_t lds_t = 0;
+    int n_rec = 0;
+    for (;; pad = false) {
+      const size_t lds_e = pad ? lds + (size_t)pad_cells_2d(M.n_rad, M.nz) * sizeof(double) : lds_k;
+      lds_t = (lds_e + 7) / 8 * 8;
+      n_rec = lds_t < lds_cap_r ? rq_records_that_fit(pola, lds_cap_r - lds_t) : 0;
+      if (n_rec > 0 || !pad) break;
+    }
     // (more records than twice the lanes buy nothing; small models keep their LDS footprint small)
     if (n_rec > 2 * rthreads) n_rec = 2 * rthreads > RQ_MIN_REC ? 2 * rthreads : RQ_MIN_REC;
     // (the optional radiation-field accumulators are kept by the single-role kernel)
@@ -1693,7 +1741,7 @@ static int launch_mega(mcgpu_ctx* ctx, const RunArgs& A, bool use_lds, int grid_
       // ms at 16 / 24 / 32 / 48) -- told apart like the tail hand-over, by the model's midplane optical depth
       int k_short = tune("MCGPU_K_SHORT", 2, 0, 64), fly_iters = tune("MCGPU_FLY_ITERS", ctx->tau_midplane > 1000.0 ? 16 : 32, 1, 256);
       int fly_idle = tune("MCGPU_FLY_IDLE", 32, 1, 65), emit_qmax = tune("MCGPU_EMIT_QMAX", 128, 0, 1 << 20);
-      const void* fn = kpick_roles(l3d, pola, dark, use_lds, M.mrw != 0);   // (the walk: 2D; 3D was sent to the single-role kernel above)
+      const void* fn = kpick_roles(l3d, pola, dark, use_lds, M.mrw != 0, pad);   // (the walk: 2D; 3D was sent to the single-role kernel above)
       // 2D grids: the launch's last packets go to the tail kernel (one packet per wave, mc_tail.hip.h) once a
       // workgroup has no more than opt_tail of them left
       RunArgs At = A;
@@ -1704,11 +1752,11 @@ static int launch_mega(mcgpu_ctx* ctx, const RunArgs& A, bool use_lds, int grid_
         HIPCHK(hipMemsetAsync(ctx->d_carry_n, 0, 2 * sizeof(unsigned int), ctx->stream));
         At.carry_out = ctx->d_carry[0]; At.carry_out_n = ctx->d_carry_n; At.carry_cap = (unsigned int)carry_cap(ctx);
         At.tail_threshold = tail_thr;
-        fn = kpick_roles_tail(pola, dark, use_lds, M.mrw != 0);
+        fn = kpick_roles_tail(pola, dark, use_lds, M.mrw != 0, pad);
       }
       // option "crossing" = 1: the flying waves cross with the flight-parametric form (fly_step_2d_param, mc_roles.hip.h) --
       // not the reference's arithmetic (statistical parity only), so never by default; 2D, LDS deposits, no dark zone, no walk
-      if (ctx->opt_crossing == 1 && !l3d && !dark && use_lds && !M.mrw) fn = kpick_roles_param(pola, tail);
+      if (param) fn = kpick_roles_param(pola, tail);
       HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));
       void* args[] = {(void*)&M, (void*)&At, (void*)&n_rec, (void*)&n_srv_pref, (void*)&k_short, (void*)&fly_iters, (void*)&fly_idle, (void*)&emit_qmax};
       HIPCHK(hipLaunchKernel(fn, dim3(rblocks), dim3(rthreads), args, lds_r, ctx->stream));

@@ -4,7 +4,7 @@
 
 Compiles mcfost_amd/csrc/kern_roles.hip (and kern_tail.hip, for the register report) with the library's flags plus
 --cuda-device-only -S into a temporary directory, cuts out the function of one instantiation (default: the Pascucci
-headline's k_thermal_roles<false,false,false,true,false>) and finds its flying loop: the innermost natural loop whose body
+headline's k_thermal_roles<false,false,false,true,false,true>: the padded cell key) and finds its flying loop: the innermost natural loop whose body
 holds the LDS deposit (ds_add_f64).  The loop's blocks are split into the common path and the rare blocks, and each part
 is counted by kind.  Rare are the blocks that hold the stop's division (v_div_scale_f64), the default-real zj fallback
 (v_cvt_f32_f64) or the runaway store (global_store), and every block that one of these dominates, unless it also
@@ -32,11 +32,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 CSRC = os.path.join(ROOT, "mcfost_amd", "csrc")
 
-PASCUCCI = "_ZN5mcgpu15k_thermal_rolesILb0ELb0ELb0ELb1ELb0EEEvNS_8DevModelENS_7RunArgsEiiiiii"
+PASCUCCI = "_ZN5mcgpu15k_thermal_rolesILb0ELb0ELb0ELb1ELb0ELb1EEEvNS_8DevModelENS_7RunArgsEiiiiii"
 REG_REPORT = [
-    ("kern_roles.hip", PASCUCCI, "k_thermal_roles<false,false,false,true,false> (Pascucci)"),
-    ("kern_tail.hip", "_ZN5mcgpu20k_thermal_roles_tailILb1ELb0ELb1ELb0EEEvNS_8DevModelENS_7RunArgsEiiiiii",
-     "k_thermal_roles_tail<true,false,true,false> (ref4.1 2D)"),
+    ("kern_roles.hip", PASCUCCI, "k_thermal_roles<false,false,false,true,false,true> (Pascucci)"),
+    ("kern_tail.hip", "_ZN5mcgpu20k_thermal_roles_tailILb1ELb0ELb1ELb0ELb0EEEvNS_8DevModelENS_7RunArgsEiiiiii",
+     "k_thermal_roles_tail<true,false,true,false,false> (ref4.1 2D)"),
     ("kern_tail.hip", "_ZN5mcgpu6k_tailILb0ELb1ELb0ELb0EEEvNS_8DevModelENS_7RunArgsEPKvPKjPj",
      "k_tail<false,true,false,false>"),
 ]
