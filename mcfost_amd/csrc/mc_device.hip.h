@@ -191,8 +191,9 @@ struct DevModel {
   const double* kappa_abs;
   const float* albedo;
   // (2D cylindrical grids: each table is followed by its copy in the padded layout of mc_roles.hip.h (pad_cells_2d values,
-  // the halo 0), for the role kernels that name a cell by its padded key)
-  const double* kappa_factor;  // [n_cells], then one 0 for "no cell" [, then the padded copy]
+  // the halo 0), for the role kernels that name a cell by its padded key; behind the padded factors, at the next multiple
+  // of 32 bytes, the cells' wall records (WallRec, mc_roles.hip.h: 32 bytes per padded cell))
+  const double* kappa_factor;  // [n_cells], then one 0 for "no cell" [, then the padded copy, then the wall records]
   const unsigned char* dark;   // [n_cells] [, then the padded copy] or null
   // scattering
   int nang, aniso_method, lisotropic, p_lambda_fixed;

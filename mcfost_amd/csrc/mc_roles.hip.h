@@ -171,6 +171,7 @@ struct Flight {
   int lam;  // (VAR: the packet's wavelength, for the per-cell opacities)
   int ic;   // (2D crossing: the 0-based index of the cell (ri, zj), n_cells outside the real cells; flight_constants sets it.
             // PAD: the padded key of (ri, zj), see below)
+  double zw;  // (PAD: the vertical wall ahead in this cell, from its WallRec; the flying waves' crossing reads it)
 };
 
 // PAD: one name for a cell of a 2D grid.  The crossing names the cell (ri, zj) three ways -- the key of the star's cell, the
@@ -214,8 +215,69 @@ __device__ __forceinline__ double pad_load_kf(const double* kf_pad, int K) {
   return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(kf_pad) + ((unsigned int)K << 3));
 }
 
+// The vertical wall of a padded cell.  Section 2 of fly_geom_2d forms the wall ahead from (ri, zj, away) and the sign of
+// z: index, row read, conversion, product, correction factor, the 1e10 above the disk, the sign -- about 30 VALU
+// instructions per crossing that do not depend on where in the cell the packet is.  Before the sign of z is applied the
+// wall is a function of (ri, zj, away) alone: two constants per padded cell, which travel with the cell's kappa_factor
+// in ONE 32-byte record
+//   { z_dn, kf, z_up, kf }      z_dn: the wall ahead of a packet that flies towards the midplane, z_up: away from it
+// so that the 16 bytes at offset 0 are (z_dn, kf) and the 16 bytes at offset 16 (z_up, kf): the flying waves' one load per
+// cell entered (fly_visit_step_2d) takes the half its direction asks for, and the pair arrives in the same two
+// registers either way -- no select tells the factor from the wall.  Records are 32-byte aligned: no half straddles a
+// 64-byte line, and a crossing touches as many lines as the 8-byte load of the factor alone did.
+//   z_up = what section 2 forms for away = true:  (double)(below ? jm : 1) * (below ? ch : zmax), jm = zj, times correct_plus
+//          as fma(zmag, +e, zmag), and 1e10 in the row zj = nz + 1 (no wall above the disk)
+//   z_dn = the same for away = false: jm = zj - 1 (1 in the row zj = 1), times correct_moins as fma(zmag, -e, zmag); in
+//          the row zj = 1, where the packet goes through the midplane to the mirror side (`flip`), stored NEGATIVE
+// and the crossing's wall is zl = (z0 < 0.0) ? -stored : stored, the same bits as section 2's
+// zmag | ((z0 < 0.0) != flip ? sign : 0) (zmag > 0).  The halo: the hole (ri = 0) and the outside column take the
+// rows T.row gives those radial indices (lds_stage: column 1 and column n_rad), the row above the disk is formed like
+// any other; the row zj = 0 is no cell of a 2D grid (zj >= 1) and holds zeros.  All entries are finite.
+struct alignas(32) WallRec {
+  double z_dn, kf_dn, z_up, kf_up;
+};
+static_assert(sizeof(WallRec) == 32, "one record: 32 bytes");
+// the wall before z's sign is applied; ch, zmax: of the column (RowT::ch, RowT::zmax of ri).  Host and device run these
+// very expressions; the correction is a true fused multiply-add on both (__builtin_fma: the device's v_fma_f64, on the
+// host the FMA3 instruction or libm's correctly rounded fma -- never a product rounded before the sum).
+__host__ __device__ inline double pad_wall_2d(int nz, int zj, bool away, double ch, double zmax) {
+  const bool top = (zj == nz + 1);
+  const int jm = away ? zj : (zj == 1 ? 1 : zj - 1);
+  const bool below = jm < nz;
+  double zmag = (double)(below ? jm : 1) * (below ? ch : zmax);
+  zmag = __builtin_fma(zmag, away ? 0x1.68p-47 : -0x1.68p-47, zmag);
+  zmag = (away && top) ? 1.0e10 : zmag;
+  return (!away && zj == 1) ? -zmag : zmag;
+}
+// the walls of every record, from the grid (ch, zmax: n_rad columns)
+inline void pad_walls_2d(int n_rad, int nz, const double* ch, const double* zmax, WallRec* rec) {
+  for (int zj = 0; zj <= nz + 1; ++zj)
+    for (int ri = 0; ri <= n_rad + 1; ++ri) {
+      const int col = ri == 0 ? 0 : (ri - 1 < n_rad ? ri - 1 : n_rad - 1);   // (the column of T.row[ri], lds_stage)
+      WallRec& r = rec[pad_key_2d(n_rad, ri, zj)];
+      r.z_dn = zj >= 1 ? pad_wall_2d(nz, zj, false, ch[col], zmax[col]) : 0.0;
+      r.z_up = zj >= 1 ? pad_wall_2d(nz, zj, true, ch[col], zmax[col]) : 0.0;
+    }
+}
+// the factors of every record, from the padded copy of kappa_factor (the halo 0)
+inline void pad_wall_factors_2d(int n_rad, int nz, const double* kf_padded, WallRec* rec) {
+  for (int K = 0; K < pad_cells_2d(n_rad, nz); ++K) rec[K].kf_dn = rec[K].kf_up = kf_padded[K];
+}
+// where the records lie: behind the padded factors, at the next multiple of 32 bytes (the array itself is aligned to more)
+__host__ __device__ inline size_t pad_wall_offset(int n_cells, int n_rad, int nz) {
+  return ((size_t)n_cells + 1 + (size_t)pad_cells_2d(n_rad, nz) + 3) / 4 * 4;   // in doubles
+}
+__device__ __forceinline__ const WallRec* pad_wall_records(const DevModel& M) {
+  return reinterpret_cast<const WallRec*>(M.kappa_factor + pad_wall_offset(M.n_cells, M.n_rad, M.nz));
+}
+// (wall ahead, kappa_factor) of padded cell K for a packet that flies away from the midplane or towards it: one 16-byte
+// load at a 32-bit byte offset on the (wave-uniform) base
+__device__ __forceinline__ double2 pad_load_wall(const WallRec* rec, int K, bool away) {
+  return *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(rec) + (((unsigned int)K << 5) | (away ? 16u : 0u)));
+}
+
 __device__ inline void flight_clear(Flight& F) {
-  F.x = F.y = F.z = F.u = F.v = 0.0; F.w = 1.0; F.extr = 0.0; F.S0 = 1.0; F.inv_a = F.inv_w = F.kf = F.kap = F.kab = 0.0;
+  F.x = F.y = F.z = F.u = F.v = 0.0; F.w = 1.0; F.extr = 0.0; F.S0 = 1.0; F.inv_a = F.inv_w = F.kf = F.kap = F.kab = 0.0; F.zw = 0.0;
   F.ri = 0; F.zj = 1; F.k = 1; F.star_key = -1; F.st = S_EMIT; F.pk_cross = 0u; F.lam = 1; F.ic = 0;
 }
 
@@ -231,9 +293,12 @@ __device__ inline void var_cell_opacities(const DevModel& M, Flight& F, int ic) 
 // REUSE (the tail kernel, whose trapped packets start flight after flight in one cell): F.ic / F.kf still hold the last
 // flight's cell and its kappa_factor (F.ic = -1: nothing yet), and the load from HBM is skipped while the cell is the same
 // PAD: F.ic is the padded key and the factor comes from the padded table (indices that name no slot: slot 0, a halo)
-template <bool L3D, bool VAR = false, bool REUSE = false, bool PAD = false>
+// WALL: the flying waves' flights, whose crossing reads the vertical wall from the cell's record (WallRec): the factor
+// and the wall of the cell the flight starts in come from there, in one load
+template <bool L3D, bool VAR = false, bool REUSE = false, bool PAD = false, bool WALL = false>
 __device__ inline void flight_constants(const Lds& T, const DevModel& M, Flight& F, int lambda) {
   static_assert(!PAD || (!L3D && !VAR && !REUSE), "the padded key: 2D grids, one dust class, the role kernels");
+  static_assert(!WALL || PAD, "the wall records are laid out by the padded key");
   const double a = F.u * F.u + F.v * F.v;  // cylindrical_grid.f90:941-952
   F.inv_a = (a > TINY_REAL) ? 1.0 / a : HUGE_REAL;
   F.inv_w = (fabs(F.w) > TINY_REAL) ? 1.0 / F.w : copysign(HUGE_DP, F.w);
@@ -242,7 +307,13 @@ __device__ inline void flight_constants(const Lds& T, const DevModel& M, Flight&
     F.ic = in_pad ? pad_key_2d(M.n_rad, F.ri, F.zj) : 0;
     F.kap = T.kappa[lambda - 1];
     F.kab = T.kabs[lambda - 1];
-    F.kf = pad_kappa_factor(M)[F.ic];
+    if (WALL) {
+      // (the cell's record: its factor and the vertical wall ahead, for the direction the first crossing will find --
+      // w * z > 0.0 is that crossing's own product and compare, see fly_geom_2d)
+      const double2 wk = pad_load_wall(pad_wall_records(M), F.ic, F.w * F.z > 0.0);
+      F.zw = wk.x;
+      F.kf = wk.y;
+    } else F.kf = pad_kappa_factor(M)[F.ic];
     return;
   }
   const int ic_new = is_real_cell<L3D>(M.n_rad, M.nz, F.ri, F.zj) ? cell_index<L3D>(M.n_rad, M.nz, F.ri, F.zj, F.k) : M.n_cells;
@@ -523,6 +594,9 @@ __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, cons
 // fly_geom_2d: sections 1-3 of fly_step_2d (radial wall, vertical wall, nearest wall, zj of the end point), expression
 // for expression, the three rounding-level fix-ups (-> GRID_PREC) as selects.  Returns which of them applied -- bit 0:
 // s1 == 0, bit 1: t < 0, bit 2: z1 == 0 (for tests/emu/emu_fly_visit.cpp; the kernels do not read it).
+// WALL: section 2 takes the wall ahead from the flight (p.zw, the cell's WallRec for this crossing's `away`) instead of
+// forming it; WALL = false is the specification of that form (tests/emu/emu_fly_wall.cpp walks both).
+template <bool WALL = false>
 __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, const Flight& p, double& l_out, double& z1_out,
                                             int& ri1_out, int& zj1_out) {
   const int n_rad = M.n_rad, nz = M.nz;
@@ -555,14 +629,21 @@ __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, cons
   // 2) vertical wall
   const double dz = w * z0;
   const bool away = dz > 0.0;
-  const bool flip = !away && (zj0 == 1);
-  const int jm = away ? zj0 : (zj0 == 1 ? 1 : zj0 - 1);
-  const bool below = jm < nz;
-  double zmag = (double)(below ? jm : 1) * *(below ? &R0.ch : &R0.zmax);
-  zmag = __builtin_fma(zmag, __longlong_as_double(away ? 0x3D06800000000000ll : (long long)0xBD06800000000000ull), zmag);
-  zmag = (away && top) ? 1.0e10 : zmag;
-  const bool neg = (z0 < 0.0) != flip;
-  const double zl = __longlong_as_double(__double_as_longlong(zmag) | (neg ? (long long)0x8000000000000000ull : 0ll));
+  double zl;
+  if (WALL) {
+    // (the record's wall carries everything but the side of the midplane the packet is on; the compare, not z0's sign
+    // bit: a stopping point can be -0.0)
+    zl = (z0 < 0.0) ? -p.zw : p.zw;
+  } else {
+    const bool flip = !away && (zj0 == 1);
+    const int jm = away ? zj0 : (zj0 == 1 ? 1 : zj0 - 1);
+    const bool below = jm < nz;
+    double zmag = (double)(below ? jm : 1) * *(below ? &R0.ch : &R0.zmax);
+    zmag = __builtin_fma(zmag, __longlong_as_double(away ? 0x3D06800000000000ll : (long long)0xBD06800000000000ull), zmag);
+    zmag = (away && top) ? 1.0e10 : zmag;
+    const bool neg = (z0 < 0.0) != flip;
+    zl = __longlong_as_double(__double_as_longlong(zmag) | (neg ? (long long)0x8000000000000000ull : 0ll));
+  }
   const int delta_zj = away ? (top ? 0 : 1) : ((zj0 == 1) ? 1 : -1);
   double t = (zl - z0) * p.inv_w;
   fix |= ((t < 0.0) && !((dz == 0.0) || hole)) ? 2 : 0;
@@ -600,12 +681,18 @@ __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, cons
 // padded tables (pad_kappa_factor, pad_dark: the caller forms the addresses once).  The star test is one compare of two
 // carried registers, the deposit is unconditional, and the next cell's key is one multiply-add that is also the offset of
 // its factor -- no "no cell" anywhere.
-template <bool DARK, bool LDSE, bool MRW = false, bool VAR = false, bool PAD = false>
+// WALL (with PAD; see WallRec): the vertical wall ahead travels with the flight (p.zw) and is not formed again.  `wall`
+// is the table of the cells' records; the lanes that move on load from it, in place of the factor alone, the pair
+// (wall ahead, kappa_factor) of the cell they enter -- still one load per crossing, issued one crossing ahead of its use.
+// They hold z1 and w, so they know which wall the next crossing will ask for: away' = (w * z1 > 0.0) is that crossing's
+// own product and compare.  WALL = false is the specification (tests/emu/emu_fly_wall.cpp).
+template <bool DARK, bool LDSE, bool MRW = false, bool VAR = false, bool PAD = false, bool WALL = false>
 __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& M, const RunArgs& A, double* E_lds, Flight& p,
                                                   unsigned int& c_dark, const double* kf_pad = nullptr,
-                                                  const unsigned char* dark_pad = nullptr) {
+                                                  const unsigned char* dark_pad = nullptr, const WallRec* wall = nullptr) {
   static_assert((1.0 + GRID_PREC) - 1.0 == 0x1.68p-47 && 1.0 - (1.0 - GRID_PREC) == 0x1.68p-47, "grid_prec is not 45 ulp");
   static_assert(!PAD || (LDSE && !VAR), "the padded key: LDS deposits, one dust class");
+  static_assert(!WALL || PAD, "the wall records are laid out by the padded key");
   if (p.st == S_FLIGHT) {
     const int n_rad = M.n_rad, nz = M.nz;
     const int ri0 = p.ri, zj0 = p.zj;
@@ -624,7 +711,7 @@ __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& 
       const double x0 = p.x, y0 = p.y, z0 = p.z, u = p.u, v = p.v, w = p.w;
       double l, z1;
       int ri1, zj1;
-      fly_geom_2d(T, M, p, l, z1, ri1, zj1);
+      fly_geom_2d<WALL>(T, M, p, l, z1, ri1, zj1);
       // 4) optical depth of the crossing, stop or go on (kf was loaded at the end of the previous crossing)
       const double tau = l * (p.kap * p.kf);
       // (what both ways share is committed once, in front of the branch)
@@ -653,14 +740,20 @@ __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& 
           c_dark += 1u;
           p.st = S_INTERACT;
         } else {
-          const double2 kk1 = VAR ? M.v_kk[(size_t)ic1 * M.n_lambda + (p.lam - 1)]
-                                  : make_double2(PAD ? pad_load_kf(kf_pad, ic1) : M.kappa_factor[ic1], 0.0);
+          if (WALL) {
+            const double2 wk = pad_load_wall(wall, ic1, w * z1 > 0.0);
+            p.zw = wk.x;
+            p.kf = wk.y;
+          } else {
+            const double2 kk1 = VAR ? M.v_kk[(size_t)ic1 * M.n_lambda + (p.lam - 1)]
+                                    : make_double2(PAD ? pad_load_kf(kf_pad, ic1) : M.kappa_factor[ic1], 0.0);
+            p.kf = kk1.x;
+            if (VAR) p.kab = kk1.y;
+          }
           p.x = __builtin_fma(l, u, x0);
           p.y = __builtin_fma(l, v, y0);
           p.z = z1;
           p.ri = ri1; p.zj = zj1; p.ic = ic1;
-          p.kf = kk1.x;
-          if (VAR) p.kab = kk1.y;
         }
       }
     }
@@ -1052,6 +1145,12 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
   const Lds T = lds_carve(lds_base + e_cells, M);
   lds_stage(T, M);
   const double* const kf_pad = PAD ? pad_kappa_factor(M) : nullptr;
+  // WALL: the flying waves take the vertical wall ahead from the cell's record (WallRec) -- the padded instantiations
+  // without a dark zone.  With DARK the flying loop holds the mirror's test and its second gather, and one instantiation
+  // (k_thermal_roles_tail<false,true,true,false,true>) then reloads a spilled flight constant from scratch inside the loop:
+  // those keep forming the wall.
+  constexpr bool WALL = PAD && !DARK;
+  const WallRec* const wall_rec = WALL ? pad_wall_records(M) : nullptr;
   const unsigned char* const dark_pad = (PAD && DARK) ? pad_dark(M) : nullptr;
   const int key_bias = PAD ? pad_star_bias(M.n_rad, M.nz) : 0;   // a record's star_key = the padded key of that cell + key_bias
   DepCache DC;
@@ -1222,7 +1321,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         }
         st = S_FLIGHT;
         if (VORO) { F.kap = T.kappa[bag_lambda - 1]; F.kab = T.kabs[bag_lambda - 1]; }
-        else flight_constants<L3D, VAR, false, PAD>(T, M, F, bag_lambda);
+        else flight_constants<L3D, VAR, false, PAD, WALL>(T, M, F, bag_lambda);   // (WALL: with the cell's wall, see WallRec)
       }
       // stopped packets that found no flight to swap with go to a free record
       {
@@ -1288,7 +1387,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
             else finished += fly_step_3d<DARK, LDSE, BIN, VAR, true, MRW>(T, M, A, E_lds, F, c_cross, c_kill, c_dark, dep_ic, dep_v);
             if (BIN) bin_deposit(BS, A.bin, A.E_abs, lane, BP, dep_ic >= 0, dep_ic, dep_v);
           } else {
-            fly_visit_step_2d<DARK, LDSE, MRW, VAR, PAD>(T, M, A, E_lds, F, c_dark, kf_pad, dark_pad);
+            fly_visit_step_2d<DARK, LDSE, MRW, VAR, PAD, WALL>(T, M, A, E_lds, F, c_dark, kf_pad, dark_pad, wall_rec);
             if (__popcll(__ballot(F.st != S_FLIGHT)) >= fly_idle) break;  // (the same vote, taken behind the crossing)
           }
         }
@@ -1774,8 +1873,8 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
 #define MCGPU_ROLES_BLOCK 1024  // threads of a workgroup of this schedule: 128 VGPRs, 4 waves per SIMD
 #endif
 
-// PADK: the padded cell key (2D, LDSE; DevModel::kappa_factor must carry the padded copy, the private grid has
-// pad_cells_2d slots); without it the kernel is the plain form, which the launcher keeps for optically thick disks
+// PADK: the padded cell key (2D, LDSE; DevModel::kappa_factor must carry the padded copy and the wall records, the private
+// grid has pad_cells_2d slots); without it the kernel is the plain form, which the launcher keeps for optically thick disks
 template <bool L3D, bool POLA, bool DARK, bool LDSE, bool MRW = false, bool PADK = false>
 __global__ void __launch_bounds__(MCGPU_ROLES_BLOCK) k_thermal_roles(const DevModel M, const RunArgs A, int n_rec, int n_srv_pref,
                                                                      int k_short, int fly_iters, int fly_idle, int emit_qmax) {

@@ -157,6 +157,9 @@ struct mcgpu_ctx {
   std::vector<double> h_kf;
   std::vector<unsigned char> h_dark;
   int pad_n_rad = 0, pad_nz = 0;
+  // the wall records of a 2D cylindrical grid (WallRec, mc_roles.hip.h): the walls are written where the grid is set, the
+  // factors where the opacities are uploaded, the device's copy lies behind the padded factors
+  std::vector<WallRec> h_wall;
   double tau_midplane = -1.0;      // radial optical depth of the midplane at the most opaque wavelength (-1: unknown)
   double last_inter_pp = -1.0;     // interactions per packet of the context's last completed thermal launch (-1: none yet)
   DevArr<unsigned int> d_tail_next;     // the tail kernel's work counter
@@ -445,6 +448,12 @@ extern "C" int mcgpu_set_grid_cyl(mcgpu_ctx* ctx, int n_rad, int nz, int n_az, i
   bin_release(ctx);
   grid_release(ctx);   // (d_prob_E, xN_abs, xJ_abs were sized for the old grid)
   ctx->have_grid = true;
+  // the walls' half of the wall records: a function of the grid alone (the factors' half: upload_cell_opacities)
+  ctx->h_wall.clear();
+  if (!l3D) {
+    ctx->h_wall.assign((size_t)pad_cells_2d(n_rad, nz), WallRec{0.0, 0.0, 0.0, 0.0});
+    pad_walls_2d(n_rad, nz, ch.data(), zmax, ctx->h_wall.data());
+  }
   // (opacities set before this grid: their padded copies are laid out for the grid they came with)
   if (ctx->have_opacity && ctx->h_kf.size() == (size_t)n_cells && (rc = upload_cell_opacities(ctx))) return rc;
   return MCGPU_OK;
@@ -789,15 +798,25 @@ extern "C" int mcgpu_set_stars(mcgpu_ctx* ctx, int n_stars, const double* x, con
 
 // kappa_factor and the dark flags on the device, from the context's host copies: the plain tables (the factors end in one
 // 0 for "no cell": the 2D crossing reads it for the virtual cells, mc_roles.hip.h) and, on a 2D cylindrical grid, their
-// copies in the padded layout behind them (DevModel::kappa_factor).  Called when the opacities or the grid are set.
+// copies in the padded layout behind them (DevModel::kappa_factor) and, behind the padded factors, the wall records: the
+// walls as mcgpu_set_grid_cyl wrote them, the factors from the padded copy.  Called when the opacities or the grid are
+// set, so that either order of the two leaves both halves of a record current.
 static int upload_cell_opacities(mcgpu_ctx* ctx) {
   DevModel& M = ctx->M;
   const bool pad = !ctx->voro && !M.grid_sph && !M.l3D;
   const size_t np = pad ? (size_t)pad_cells_2d(M.n_rad, M.nz) : 0;
+  if (pad && ctx->h_wall.size() != np) return fail(ctx, MCGPU_ERR_STATE, "no wall records for this grid");
   int rc;
-  std::vector<double> kfp((size_t)M.n_cells + 1 + np, 0.0);
+  // (2D: the wall records behind the padded copy, 32-byte aligned in an array that hipMalloc aligns to more)
+  const size_t wall_at = pad ? pad_wall_offset(M.n_cells, M.n_rad, M.nz) : 0;
+  std::vector<double> kfp(pad ? wall_at + 4 * np : (size_t)M.n_cells + 1, 0.0);
   std::memcpy(kfp.data(), ctx->h_kf.data(), (size_t)M.n_cells * sizeof(double));
-  if (pad) pad_table_2d(M.n_rad, M.nz, ctx->h_kf.data(), kfp.data() + M.n_cells + 1);
+  if (pad) {
+    double* const padded = kfp.data() + M.n_cells + 1;
+    pad_table_2d(M.n_rad, M.nz, ctx->h_kf.data(), padded);
+    pad_wall_factors_2d(M.n_rad, M.nz, padded, ctx->h_wall.data());
+    std::memcpy(kfp.data() + wall_at, ctx->h_wall.data(), np * sizeof(WallRec));
+  }
   if ((rc = upload(ctx, kfp.data(), kfp.size(), &M.kappa_factor))) return rc;
   M.dark = nullptr;
   if (!ctx->h_dark.empty()) {
