@@ -692,6 +692,54 @@ int mcgpu_probe_xi_sort_fold(mcgpu_ctx *ctx, uint64_t n, const uint32_t *keys, c
                              float *xI, uint32_t *sentinel);
 
 /*
+ * The SED commit pass's ATOMIC deposit staging on deposits the caller chooses (mc_commit_probe.hip.h: the wave functions of
+ * mc_mono.hip.h run by whole workgroups; the tests give integer-valued inputs and compare bit for bit).
+ * Schedule: T = grid_blocks * block_threads threads (block_threads a multiple of 64, <= 512); global thread g handles item
+ * r * T + g in round r of n_rounds, every lane in converged flow; every per-item array has n = T * n_rounds entries.
+ *   where[n][4] = icell (1-based; 0: the lane has no deposit this round), psup, phik (1-based), flags: bit 0 = flag_star,
+ *   bit 1 = a new flight starts (mode 0: the lane's per-lane results are rewritten from this item's before the round's
+ *   deposit, otherwise those of its previous flight serve -- flag_star belongs to the flight; mode 1: `need`).
+ * mode 0, the deposits, into xI (in/out): n_cells * n_theta_rt * n_az_rt sub-bins and n_slack more behind them that must come
+ * back unchanged.  pola = Stokes tracking, contrib = lsepar_contrib.
+ *   path 0  deposit_rt1_wave -> wave_deposit_records: xI = double[sub-bin][nRT][8]; itheta[n][nRT] (0..nang), S[n][4],
+ *           with pola cosw, sinw[n][nRT]; mu[6][nang + 1] the Mueller columns (s11, then the five ratios)
+ *   path 1  deposit_rt1_wave_f32, one dust class: xI = float[sub-bin][binf] in the packed layout of (nRT, pola, contrib);
+ *           weights[n][nRT][4 with pola, else 1], placed by the function angles_scatt_rt1 places them with
+ *   path 2  deposit_rt1_wave_row: as path 1, the weights placed as the lane's row
+ *   path 3  deposit_rt1_wave_f32 with dust classes: the per-lane results of path 0, cell_class[n_cells] (0-based),
+ *           vtab[6][n_classes][n_lambda][nang + 1], column p_lambda (1-based)
+ *   fetched (paths 1-3, may be NULL): double[n_cells][nRT][N_type_flux][n_theta_rt][n_az_rt], what mcgpu_fetch_xI's kernel
+ *   makes of the array (with contrib: I = star + thermal).
+ * mode 1, angles_scatt_rt1 for the lanes with `need`: dir[n][3], S[n][4], the observers rt_u, rt_v[nRT], rt_w[RT_n_incl];
+ * by_wave: angles_scatt_rt1_wave, else the per-lane form; with_mu: the deposit weights (from mu) instead of the angles;
+ * row: the weights as the lane's row.  After every round every lane's results are copied out: dump_row[n][rowf], or
+ * dump_itheta[n][nRT] and, with pola, the 8 bytes of every cosw / sinw slot as dump_cosw, dump_sinw[n][nRT].
+ * MCGPU_ERR_ARG (nothing launched): a combination whose LDS exceeds 160 KB, a deposit beyond the array, a table index
+ * beyond its table, any other bad argument.  The probe uses the context's device and stream and none of its tables.
+ */
+typedef struct {
+  int mode, path, pola, contrib, by_wave, with_mu, row;
+  int grid_blocks, block_threads, n_rounds;
+  int nRT, RT_n_incl, n_cells, n_theta_rt, n_az_rt, n_slack;
+  int nang, n_classes, n_lambda, p_lambda;
+  const int *where;
+  const float *l;
+  const float *weights;
+  const int *itheta;
+  const double *cosw, *sinw, *S, *dir;
+  const float *mu;
+  const int *cell_class;
+  const float *vtab;
+  const double *rt_u, *rt_v, *rt_w;
+  void *xI;
+  double *fetched;
+  float *dump_row;
+  int *dump_itheta;
+  double *dump_cosw, *dump_sinw;
+} mcgpu_xi_commit_probe;
+int mcgpu_probe_xi_commit(mcgpu_ctx *ctx, const mcgpu_xi_commit_probe *p);
+
+/*
  * lvariable_dust (dust settling etc.; mem.f90:213-244): the opacity and re-emission tables gain the cell axis
  * p_n_cells and the loop reads them with p_icell (optical_depth.f90:100-102, radiation_field.f90:47-53,
  * dust_transfer.f90:1284, thermal_emission.f90:659-771).  Call after mcgpu_set_opacity and mcgpu_set_thermal, with

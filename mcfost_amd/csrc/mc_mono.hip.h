@@ -144,6 +144,65 @@ __device__ __forceinline__ void row_put(float* rowimg, int p, int slot, float v)
   typedef __attribute__((address_space(3))) float lds_f32_t;
   ((lds_f32_t*)rowimg)[(((size_t)(p >> 2) * blockDim.x + slot) << 2) + (p & 3)] = v;
 }
+// Where a flight's deposit weights for observer q go (the commit pass with default-real records and one dust class; the
+// three forms are described above).  F::w(t, a...) = the weight of I (t = 0) and, with Stokes tracking, of Q, U, V (1..3)
+// from the caller's six numbers: every form evaluates F's expressions where it stores them, as the code did before it was
+// one function.
+//   row:     the flight's row of the log in HBM, [nRT][4] or [nRT]
+//   rowimg:  the lane's row in LDS in the order of the sub-bin -- interleaved, split, or with I stored (no contributions)
+//   neither: the lane's per-observer slots, two float2 in the 16 bytes of (cosw, sinw), or the one weight in itheta's 4
+// One function, because the unit probe of the commit pass (mc_commit_probe.hip.h) places chosen weights with it: what
+// deposit_rt1_wave_f32 / deposit_rt1_wave_row read there is written by the code the kernels run.
+struct Rt1WeightI {       // angles_scatt_rt1_one without Stokes tracking: Stokes(1) x s11
+  static __device__ __forceinline__ float w(int, double S0, double s11, double, double, double, double) { return (float)(S0 * s11); }
+};
+struct Rt1WeightsPola {   // ... with: RPO . (D1 .. D4) (the expressions of deposit_rt1_wave, without the path length)
+  static __device__ __forceinline__ float w(int t, double D1, double D2, double D3, double D4, double cosw, double sinw) {
+    return t == 0 ? (float)D1 : t == 1 ? (float)((-cosw) * D2 + (-sinw) * D3) : t == 2 ? (float)((-sinw) * D2 + cosw * D3) : (float)D4;
+  }
+};
+struct Rt1WeightsGiven {  // the unit probe: the four weights themselves
+  static __device__ __forceinline__ float w(int t, double f0, double f1, double f2, double f3, double, double) {
+    return (float)(t == 0 ? f0 : t == 1 ? f1 : t == 2 ? f2 : f3);
+  }
+};
+template <bool POLA, typename F>
+__device__ __forceinline__ void rt1_store_weights(const MonoArgs& A, const RtScratch& R, int q, int slot, float* row, float* rowimg,
+                                                  bool star, double a0, double a1, double a2, double a3, double a4, double a5) {
+  if (!POLA) {
+    const float wI = F::w(0, a0, a1, a2, a3, a4, a5);
+    if (row) row[q] = wI;
+    else if (rowimg) {
+      const Xi32Lay& X = A.xi;
+      if (!X.sum_I) row_put(rowimg, q * X.sA, slot, wI);
+      else if (!X.split) { row_put(rowimg, q * X.sA, slot, star ? wI : 0.0f); row_put(rowimg, q * X.sA + 1, slot, star ? 0.0f : wI); }
+      else row_put(rowimg, q, slot, wI);
+    } else R.itheta[q * blockDim.x + slot] = __float_as_int(wI);
+  } else {
+    if (row) {
+      reinterpret_cast<float4*>(row)[q] = make_float4(F::w(0, a0, a1, a2, a3, a4, a5), F::w(1, a0, a1, a2, a3, a4, a5),
+                                                      F::w(2, a0, a1, a2, a3, a4, a5), F::w(3, a0, a1, a2, a3, a4, a5));
+    } else if (rowimg) {
+      const Xi32Lay& X = A.xi;
+      const float f0 = F::w(0, a0, a1, a2, a3, a4, a5), f1 = F::w(1, a0, a1, a2, a3, a4, a5), f2 = F::w(2, a0, a1, a2, a3, a4, a5),
+                  f3 = F::w(3, a0, a1, a2, a3, a4, a5);
+      if (!X.sum_I) {
+        const int b = q * X.sA;
+        row_put(rowimg, b, slot, f0); row_put(rowimg, b + 1, slot, f1); row_put(rowimg, b + 2, slot, f2); row_put(rowimg, b + 3, slot, f3);
+      } else {
+        const int b = q * X.sA;       // (interleaved: sA = 5; split: sA = 3)
+        row_put(rowimg, b, slot, f1); row_put(rowimg, b + 1, slot, f2); row_put(rowimg, b + 2, slot, f3);
+        if (X.split) row_put(rowimg, A.nRT * 3 + q, slot, f0);
+        else { row_put(rowimg, b + 3, slot, star ? f0 : 0.0f); row_put(rowimg, b + 4, slot, star ? 0.0f : f0); }
+      }
+    } else {
+      float2* wc = reinterpret_cast<float2*>(R.cosw) + (q * blockDim.x + slot);
+      float2* ws = reinterpret_cast<float2*>(R.sinw) + (q * blockDim.x + slot);
+      *wc = make_float2(F::w(0, a0, a1, a2, a3, a4, a5), F::w(1, a0, a1, a2, a3, a4, a5));
+      *ws = make_float2(F::w(2, a0, a1, a2, a3, a4, a5), F::w(3, a0, a1, a2, a3, a4, a5));
+    }
+  }
+}
 #endif
 // the scattering-angle bin k of a flight (u, v, w) towards observer q (:430-434); wr: the observer's w
 __device__ __forceinline__ int rt1_angle_bin(const DevModel& M, const MonoArgs& A, int q, double u, double v, double w, double& wr) {
@@ -179,14 +238,7 @@ __device__ inline void angles_scatt_rt1_one(const DevModel& M, const MonoArgs& A
   if (!row && !rowimg) R.itheta[q * blockDim.x + slot] = k;
 #ifndef MCGPU_LANE_EMULATION   // (the lane emulation has no default-real commit pass)
   if (!POLA && w_mu) {
-    const float wI = (float)(S[0] * (double)w_mu[k]);
-    if (row) row[q] = wI;
-    else if (rowimg) {
-      const Xi32Lay& X = A.xi;
-      if (!X.sum_I) row_put(rowimg, q * X.sA, slot, wI);
-      else if (!X.split) { row_put(rowimg, q * X.sA, slot, star ? wI : 0.0f); row_put(rowimg, q * X.sA + 1, slot, star ? 0.0f : wI); }
-      else row_put(rowimg, q, slot, wI);
-    } else R.itheta[q * blockDim.x + slot] = __float_as_int(wI);
+    rt1_store_weights<POLA, Rt1WeightI>(A, R, q, slot, row, rowimg, star, S[0], (double)w_mu[k], 0.0, 0.0, 0.0, 0.0);
   }
 #endif
   if (POLA) {
@@ -224,26 +276,7 @@ __device__ inline void angles_scatt_rt1_one(const DevModel& M, const MonoArgs& A
       const double D2 = (double)s12 * C1 + (double)s22 * C2;
       const double D3 = (double)s33 * C3 + (double)(-s34) * C4;
       const double D4 = (double)s34 * C3 + (double)s44 * C4;
-      if (row) {
-        reinterpret_cast<float4*>(row)[q] = make_float4((float)D1, (float)((-cosw) * D2 + (-sinw) * D3), (float)((-sinw) * D2 + cosw * D3), (float)D4);
-      } else if (rowimg) {
-        const Xi32Lay& X = A.xi;
-        const float f0 = (float)D1, f1 = (float)((-cosw) * D2 + (-sinw) * D3), f2 = (float)((-sinw) * D2 + cosw * D3), f3 = (float)D4;
-        if (!X.sum_I) {
-          const int b = q * X.sA;
-          row_put(rowimg, b, slot, f0); row_put(rowimg, b + 1, slot, f1); row_put(rowimg, b + 2, slot, f2); row_put(rowimg, b + 3, slot, f3);
-        } else {
-          const int b = q * X.sA;       // (interleaved: sA = 5; split: sA = 3)
-          row_put(rowimg, b, slot, f1); row_put(rowimg, b + 1, slot, f2); row_put(rowimg, b + 2, slot, f3);
-          if (X.split) row_put(rowimg, A.nRT * 3 + q, slot, f0);
-          else { row_put(rowimg, b + 3, slot, star ? f0 : 0.0f); row_put(rowimg, b + 4, slot, star ? 0.0f : f0); }
-        }
-      } else {
-        float2* wc = reinterpret_cast<float2*>(R.cosw) + (q * blockDim.x + slot);
-        float2* ws = reinterpret_cast<float2*>(R.sinw) + (q * blockDim.x + slot);
-        *wc = make_float2((float)D1, (float)((-cosw) * D2 + (-sinw) * D3));
-        *ws = make_float2((float)((-sinw) * D2 + cosw * D3), (float)D4);
-      }
+      rt1_store_weights<POLA, Rt1WeightsPola>(A, R, q, slot, row, rowimg, star, D1, D2, D3, D4, cosw, sinw);
     }
 #endif
   }
@@ -781,6 +814,16 @@ __device__ inline void deposit_rt1_wave_row(const MonoArgs& A, const float* row_
 }
 #endif
 
+// rotation()'s cost, sint, sing for the axis (-u_obs, -v_obs, -w_obs) of observer q (RtScratch::rot)
+__device__ __forceinline__ void rt1_observer_rot(const MonoArgs& A, int q, double* rot3) {
+  const double u1 = -A.rt_u[q], v1 = -A.rt_v[q], w1 = -A.rt_w[q % A.RT_n_incl];
+  double cost, sint, sing;
+  if (w1 > 0.999999999) { cost = 1.0; sint = 0.0; sing = 0.0; }
+  else if (fabs(u1) < TINY_REAL) { cost = 0.0; sint = 1.0; sing = sqrt(1.0 - w1 * w1); }
+  else { const double h = sqrt(u1 * u1 + v1 * v1); cost = u1 / h; sint = v1 / h; sing = sqrt(1.0 - w1 * w1); }
+  rot3[0] = cost; rot3[1] = sint; rot3[2] = sing;
+}
+
 // LDS of a SED-mode workgroup after the shared tables: the Mueller columns of p_lambda, the per-lane
 // results of angles_scatt_rt1 and the per-wave deposit tiles (mono_lds_bytes is the matching size).
 struct MonoLds {
@@ -831,12 +874,7 @@ __device__ inline MonoLds mono_lds_setup(const DevModel& M, const MonoArgs& A, d
   {  // rotation()'s cost, sint, sing for the axis (-u_obs, -v_obs, -w_obs): the same expressions, once per observer
     double* rot = lds_base + (used + 7) / 8;
     for (int q = threadIdx.x; q < A.nRT; q += blockDim.x) {
-      const double u1 = -A.rt_u[q], v1 = -A.rt_v[q], w1 = -A.rt_w[q % A.RT_n_incl];
-      double cost, sint, sing;
-      if (w1 > 0.999999999) { cost = 1.0; sint = 0.0; sing = 0.0; }
-      else if (fabs(u1) < TINY_REAL) { cost = 0.0; sint = 1.0; sing = sqrt(1.0 - w1 * w1); }
-      else { const double h = sqrt(u1 * u1 + v1 * v1); cost = u1 / h; sint = v1 / h; sing = sqrt(1.0 - w1 * w1); }
-      rot[3 * q] = cost; rot[3 * q + 1] = sint; rot[3 * q + 2] = sing;
+      rt1_observer_rot(A, q, rot + 3 * q);
     }
     L.R.rot = rot;
     L.kf = nullptr;

@@ -35,6 +35,7 @@
 #include "host_tail.h"
 #include "mc_xilog.hip.h"
 #include "mc_stage_probe.hip.h"
+#include "mc_commit_probe.hip.h"
 
 using namespace mcgpu;
 
@@ -4430,6 +4431,126 @@ extern "C" int mcgpu_probe_xi_sort_fold(mcgpu_ctx* ctx, uint64_t n, const uint32
   if (e != (int)hipSuccess) { ctx->err = std::string("mcgpu_probe_xi_sort_fold: sort / fold: ") + hipGetErrorString((hipError_t)e); return MCGPU_ERR_HIP; }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(d_xI.get(xI, (size_t)n_bins * xi.binf));
+  return MCGPU_OK;
+}
+
+// ---- exact-sum probe of the commit pass's atomic deposit staging (mc_commit_probe.hip.h; tests/test_xi_commit_exact.py) ----
+template <typename Tp>
+static hipError_t probe_put(DevArr<Tp>& d, const Tp* h, size_t n) {
+  const hipError_t e = d.resize(n);
+  return e != hipSuccess || !n ? e : d.put(h, n);
+}
+
+extern "C" int mcgpu_probe_xi_commit(mcgpu_ctx* ctx, const mcgpu_xi_commit_probe* p) {
+  if (!ctx) return MCGPU_ERR_ARG;
+  const char* const bad = "mcgpu_probe_xi_commit: bad argument";
+  if (!p || (p->mode != 0 && p->mode != 1) || p->path < 0 || p->path > 3 || !p->where || !p->mu) return fail(ctx, MCGPU_ERR_ARG, bad);
+  if (p->grid_blocks < 1 || p->grid_blocks > 64 || p->block_threads < 64 || p->block_threads > 512 || p->block_threads % 64)
+    return fail(ctx, MCGPU_ERR_ARG, bad);
+  if (p->n_rounds < 1 || p->n_rounds > 4096 || p->nRT < 1 || p->nRT > 64 || p->nang < 1 || p->nang > 4096) return fail(ctx, MCGPU_ERR_ARG, bad);
+  const bool pola = p->pola != 0, contrib = p->contrib != 0, dep = p->mode == 0;
+  const bool f32 = dep ? p->path != 0 : p->row != 0, row = dep ? p->path == 2 : p->row != 0, var = dep && p->path == 3;
+  const int nRT = p->nRT, nv = pola ? 4 : 1, na1 = p->nang + 1;
+  const size_t T = (size_t)p->grid_blocks * p->block_threads, n = T * p->n_rounds;
+  const Xi32Lay xi = xi32_layout(nRT, pola, contrib);
+  const int rowf = row ? xi32_row_floats(xi, nRT) : 0;
+  const XiCommitProbeLds lds = xi_commit_probe_lds(p->nang, nRT, p->block_threads, pola, rowf);
+  if (lds.bytes > (size_t)160 * 1024) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_xi_commit: the per-lane results and the tiles do not fit in LDS");
+  size_t n_sub = 0, n_alloc = 0;
+  if (dep) {
+    if (p->n_cells < 1 || p->n_theta_rt < 1 || p->n_az_rt < 1 || p->n_slack < 0 || !p->xI || !p->l) return fail(ctx, MCGPU_ERR_ARG, bad);
+    n_sub = (size_t)p->n_cells * p->n_theta_rt * p->n_az_rt;
+    n_alloc = n_sub + (size_t)p->n_slack;
+    if (n_alloc > (1u << 20)) return fail(ctx, MCGPU_ERR_ARG, bad);
+    if (p->path == 0 || var) { if (!p->itheta || !p->S || (pola && (!p->cosw || !p->sinw))) return fail(ctx, MCGPU_ERR_ARG, bad); }
+    else if (!p->weights) return fail(ctx, MCGPU_ERR_ARG, bad);
+    if (var && (p->n_classes < 1 || p->n_lambda < 1 || p->p_lambda < 1 || p->p_lambda > p->n_lambda || !p->cell_class || !p->vtab))
+      return fail(ctx, MCGPU_ERR_ARG, bad);
+    // every deposit lands in a sub-bin of the array, every table index inside its table
+    for (size_t i = 0; i < n; ++i) {
+      const int* w = p->where + 4 * i;
+      if (w[0] < 0 || w[0] > p->n_cells || (w[0] && (w[1] < 1 || w[1] > p->n_theta_rt || w[2] < 1 || w[2] > p->n_az_rt)))
+        return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_xi_commit: a deposit beyond the array");
+      if (p->path == 0 || var)
+        for (int q = 0; q < nRT; ++q)
+          if (p->itheta[i * nRT + q] < 0 || p->itheta[i * nRT + q] > p->nang) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_xi_commit: a scattering-angle bin beyond the tables");
+    }
+    if (var) for (int c = 0; c < p->n_cells; ++c) if (p->cell_class[c] < 0 || p->cell_class[c] >= p->n_classes) return fail(ctx, MCGPU_ERR_ARG, bad);
+  } else {
+    if (!p->dir || !p->S || !p->rt_u || !p->rt_v || !p->rt_w || p->RT_n_incl < 1 || nRT % p->RT_n_incl) return fail(ctx, MCGPU_ERR_ARG, bad);
+    if (row ? !p->dump_row : (!p->dump_itheta || (pola && (!p->dump_cosw || !p->dump_sinw)))) return fail(ctx, MCGPU_ERR_ARG, bad);
+    if (row && !p->with_mu) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_xi_commit: a row holds weights");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  DevArr<int> d_where, d_itheta, d_class, d_dit;
+  DevArr<float> d_l, d_w, d_mu, d_vtab, d_x32, d_drow;
+  DevArr<double> d_cosw, d_sinw, d_S, d_dir, d_u, d_v, d_rw, d_x64, d_fetch, d_dcw, d_dsw;
+  DevModel M;
+  memset(&M, 0, sizeof(M));
+  MonoArgs A;
+  memset(&A, 0, sizeof(A));
+  XiCommitProbe P;
+  memset(&P, 0, sizeof(P));
+  HIPCHK(probe_put(d_where, p->where, 4 * n)); P.where = d_where;
+  HIPCHK(probe_put(d_mu, p->mu, (size_t)6 * na1)); P.mu = d_mu;
+  M.nang = p->nang; M.n_cells = p->n_cells;
+  A.nRT = nRT; A.RT_n_incl = dep ? nRT : p->RT_n_incl; A.contrib = contrib ? 1 : 0; A.N_type_flux = nv + (contrib ? 4 : 0);
+  A.n_theta_rt = p->n_theta_rt; A.n_az_rt = p->n_az_rt; A.p_lambda = var ? p->p_lambda : 1; A.lambda = 1; A.rt1 = 1;
+  A.xI_f32 = f32 ? 1 : 0; A.xi = xi; A.rowf = rowf; A.flags = 0;
+  P.mode = p->mode; P.path = p->path; P.n_rounds = p->n_rounds; P.by_wave = p->by_wave; P.with_mu = p->with_mu;
+  const size_t xI_floats = n_alloc * (size_t)xi.binf, xI_doubles = n_alloc * (size_t)nRT * XI_LINE;
+  if (dep) {
+    HIPCHK(probe_put(d_l, p->l, n)); P.l = d_l;
+    if (p->path == 0 || var) {
+      HIPCHK(probe_put(d_itheta, p->itheta, n * nRT)); P.itheta = d_itheta;
+      HIPCHK(probe_put(d_S, p->S, 4 * n)); P.S = d_S;
+      if (pola) { HIPCHK(probe_put(d_cosw, p->cosw, n * nRT)); HIPCHK(probe_put(d_sinw, p->sinw, n * nRT)); P.cosw = d_cosw; P.sinw = d_sinw; }
+    } else {
+      HIPCHK(probe_put(d_w, p->weights, n * nRT * nv)); P.weights = d_w;
+    }
+    if (var) {
+      const size_t nt = (size_t)p->n_classes * p->n_lambda * na1;
+      HIPCHK(probe_put(d_class, p->cell_class, (size_t)p->n_cells)); HIPCHK(probe_put(d_vtab, p->vtab, 6 * nt));
+      M.n_classes = p->n_classes; M.n_lambda = p->n_lambda; M.cell_class = d_class;
+      M.v_s11 = d_vtab.p; M.v_s12 = d_vtab.p + nt; M.v_s22 = d_vtab.p + 2 * nt; M.v_s33 = d_vtab.p + 3 * nt;
+      M.v_s34 = d_vtab.p + 4 * nt; M.v_s44 = d_vtab.p + 5 * nt;
+    }
+    if (f32) { HIPCHK(probe_put(d_x32, (const float*)p->xI, xI_floats)); A.xI = reinterpret_cast<double*>(d_x32.p); }
+    else { HIPCHK(probe_put(d_x64, (const double*)p->xI, xI_doubles)); A.xI = d_x64; }
+  } else {
+    HIPCHK(probe_put(d_dir, p->dir, 3 * n)); P.dir = d_dir;
+    HIPCHK(probe_put(d_S, p->S, 4 * n)); P.S = d_S;
+    HIPCHK(probe_put(d_u, p->rt_u, (size_t)nRT)); HIPCHK(probe_put(d_v, p->rt_v, (size_t)nRT)); HIPCHK(probe_put(d_rw, p->rt_w, (size_t)p->RT_n_incl));
+    A.rt_u = d_u; A.rt_v = d_v; A.rt_w = d_rw;
+    if (row) { HIPCHK(d_drow.resize(n * rowf)); P.dump_row = d_drow; }
+    else {
+      HIPCHK(d_dit.resize(n * nRT)); P.dump_itheta = d_dit;
+      if (pola) { HIPCHK(d_dcw.resize(n * nRT)); HIPCHK(d_dsw.resize(n * nRT)); P.dump_cosw = d_dcw; P.dump_sinw = d_dsw; }
+    }
+  }
+  const void* fn = pola ? (const void*)k_probe_xi_commit<true> : (const void*)k_probe_xi_commit<false>;
+  HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds.bytes));
+  if (pola) hipLaunchKernelGGL((k_probe_xi_commit<true>), dim3(p->grid_blocks), dim3(p->block_threads), lds.bytes, ctx->stream, M, A, P);
+  else hipLaunchKernelGGL((k_probe_xi_commit<false>), dim3(p->grid_blocks), dim3(p->block_threads), lds.bytes, ctx->stream, M, A, P);
+  HIPCHK(hipGetLastError());
+  if (dep && f32 && p->fetched) {   // what mcgpu_fetch_xI makes of the packed array
+    const size_t nf = (size_t)p->n_cells * nRT * A.N_type_flux * p->n_theta_rt * p->n_az_rt;
+    HIPCHK(d_fetch.resize(nf));
+    hipLaunchKernelGGL(k_xI_fetch, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, ctx->stream, A.xI, (float*)nullptr, d_fetch.p,
+                       p->n_az_rt, p->n_theta_rt, A.N_type_flux, nRT, nf, 1, xi, nv);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(d_fetch.get(p->fetched, nf));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (dep) {
+    if (f32) HIPCHK(d_x32.get((float*)p->xI, xI_floats));
+    else HIPCHK(d_x64.get((double*)p->xI, xI_doubles));
+  } else if (row) HIPCHK(d_drow.get(p->dump_row, n * rowf));
+  else {
+    HIPCHK(d_dit.get(p->dump_itheta, n * nRT));
+    if (pola) { HIPCHK(d_dcw.get(p->dump_cosw, n * nRT)); HIPCHK(d_dsw.get(p->dump_sinw, n * nRT)); }
+  }
   return MCGPU_OK;
 }
 

@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "mcgpu_set_grid_sph", "mcgpu_temp_approx_diffusion_vertical", "mcgpu_set_mrw", "mcgpu_fetch_radiation_field", "mcgpu_set_variable_dust", "mcgpu_rt1_stars_map_sed", "mcgpu_define_dark_zone", "mcgpu_init_reemission", "mcgpu_multi_create", "mcgpu_multi_destroy", "mcgpu_multi_size", "mcgpu_multi_ctx", "mcgpu_multi_last_error",
     "mcgpu_repartition_energie", "mcgpu_opacity", "mcgpu_set_variable_dust_s11", "mcgpu_set_scattering_method1", "mcgpu_set_rt2", "mcgpu_fetch_I_spec", "mcgpu_rt1_stars_map_image", "mcgpu_set_I_spec", "mcgpu_rt2_source", "mcgpu_rt2_dust_map", "mcgpu_rt2_image", "mcgpu_shard_packets", "mcgpu_multi_run_thermal", "mcgpu_multi_run_mono", "mcgpu_multi_run_sed", "mcgpu_multi_rccl_ranks", "mcgpu_multi_create_ex", "mcgpu_multi_reductions", "mcgpu_set_mrw_exit_spectrum", "mcgpu_voronoi_tesselation", "mcgpu_build_ksca_CDF", "mcgpu_init_reemission_ex", "mcgpu_tau_maps",
     "mcgpu_set_nlte", "mcgpu_init_reemission_nlte", "mcgpu_set_J0", "mcgpu_temp_finale_nlte", "mcgpu_set_Tdust_1grain",
-    "mcgpu_probe_reemission_nlte", "mcgpu_probe_bin_stage", "mcgpu_probe_xi_sort_fold",
+    "mcgpu_probe_reemission_nlte", "mcgpu_probe_bin_stage", "mcgpu_probe_xi_sort_fold", "mcgpu_probe_xi_commit",
 )
 
 
@@ -81,6 +81,15 @@ class RtOpts(C.Structure):
 class SedWavelength(C.Structure):
     _fields_ = [("lambda_", C.c_int), ("p_lambda", C.c_int), ("wl_um", C.c_double), ("E_star", C.c_double),
                 ("E_ISM", C.c_double), ("seed", C.c_uint64), ("cost", C.c_double)]
+
+
+class XiCommitProbe(C.Structure):    # mcgpu_xi_commit_probe
+    _fields_ = [(k, C.c_int) for k in ("mode", "path", "pola", "contrib", "by_wave", "with_mu", "row", "grid_blocks",
+                                       "block_threads", "n_rounds", "nRT", "RT_n_incl", "n_cells", "n_theta_rt", "n_az_rt",
+                                       "n_slack", "nang", "n_classes", "n_lambda", "p_lambda")] + \
+               [(k, C.c_void_p) for k in ("where", "l", "weights", "itheta", "cosw", "sinw", "S", "dir", "mu", "cell_class",
+                                          "vtab", "rt_u", "rt_v", "rt_w", "xI", "fetched", "dump_row", "dump_itheta",
+                                          "dump_cosw", "dump_sinw")]
 
 
 _lib = None
@@ -964,6 +973,97 @@ class Engine:
             _p(cap, C.c_uint32), _p(left, C.c_uint32)), "mcgpu_probe_bin_stage")
         return dict(out=o, overflow=int(stats[0]), drained=int(stats[1]), folded=int(stats[2]), made=int(stats[3]),
                     off=off, cap=cap, counts_left=left)
+
+    def probe_xi_commit(self, path, where, l, xI, nRT, pola, contrib, grid_blocks, block_threads, n_cells, n_theta_rt, n_az_rt,
+                        mu, weights=None, itheta=None, cosw=None, sinw=None, S=None, cell_class=None, vtab=None, p_lambda=1):
+        """The commit pass's atomic deposit staging on chosen deposits (``mcgpu_probe_xi_commit`` mode 0; the schedule and
+        the arguments are described in ``include/mcgpu.h``).  ``where`` int32 ``[n, 4]``, ``l`` ``[n]``, ``xI`` the raw device
+        array (float64 ``[n_alloc, nRT, 8]`` for path 0, else float32 ``[n_alloc, binf]``; not modified), ``mu`` float32
+        ``[6, nang + 1]``, ``vtab`` float32 ``[6, n_classes, n_lambda, nang + 1]``.  Returns ``(raw, fetched)``: the array
+        after the deposits and, for the default-real paths, what the fetch kernel makes of it, float64
+        ``[n_cells, nRT, N_type_flux, n_theta_rt, n_az_rt]`` (else ``None``)."""
+        T = grid_blocks * block_threads
+        w = _a(where, np.int32)
+        n = w.shape[0]
+        assert w.shape == (n, 4) and n % T == 0
+        nv = 4 if pola else 1
+        m = _a(mu, np.float32)
+        assert m.ndim == 2 and m.shape[0] == 6
+        a = XiCommitProbe()
+        a.mode, a.path, a.pola, a.contrib = 0, path, int(pola), int(contrib)
+        a.grid_blocks, a.block_threads, a.n_rounds = grid_blocks, block_threads, n // T
+        a.nRT, a.RT_n_incl, a.n_cells, a.n_theta_rt, a.n_az_rt = nRT, nRT, n_cells, n_theta_rt, n_az_rt
+        a.nang, a.p_lambda = m.shape[1] - 1, p_lambda
+        n_sub = n_cells * n_theta_rt * n_az_rt
+        if path == 0:
+            o = np.array(xI, dtype=np.float64, order="C")
+            assert o.ndim == 3 and o.shape[1:] == (nRT, 8)
+        else:
+            o = np.array(xI, dtype=np.float32, order="C")
+            assert o.ndim == 2 and o.shape[1] == xi32_layout(nRT, pola, contrib)["binf"]
+        a.n_slack = o.shape[0] - n_sub
+        keep = [w, m, o, _a(l, np.float32)]
+        assert keep[3].shape == (n,)
+        a.where, a.mu, a.xI, a.l = w.ctypes.data, m.ctypes.data, o.ctypes.data, keep[3].ctypes.data
+
+        def give(name, x, dt, shape):
+            x = _a(x, dt)
+            assert x.shape == shape, (name, x.shape, shape)
+            keep.append(x)
+            setattr(a, name, x.ctypes.data)
+        if path in (0, 3):
+            give("itheta", itheta, np.int32, (n, nRT))
+            give("S", S, np.float64, (n, 4))
+            if pola:
+                give("cosw", cosw, np.float64, (n, nRT))
+                give("sinw", sinw, np.float64, (n, nRT))
+        else:
+            give("weights", weights, np.float32, (n, nRT, nv))
+        if path == 3:
+            vt = _a(vtab, np.float32)
+            a.n_classes, a.n_lambda = vt.shape[1], vt.shape[2]
+            give("vtab", vt, np.float32, (6, a.n_classes, a.n_lambda, m.shape[1]))
+            give("cell_class", cell_class, np.int32, (n_cells,))
+        fetched = None
+        if path != 0:
+            fetched = np.zeros((n_cells, nRT, nv + (4 if contrib else 0), n_theta_rt, n_az_rt), np.float64)
+            a.fetched = fetched.ctypes.data
+        self._chk(self.lib.mcgpu_probe_xi_commit(self.ctx, C.byref(a)), "mcgpu_probe_xi_commit")
+        return o, fetched
+
+    def probe_rt1_angles(self, dirs, S, need, star, rt_u, rt_v, rt_w, mu, pola, grid_blocks, block_threads, by_wave,
+                         with_mu=False, row=False, contrib=False):
+        """``angles_scatt_rt1`` for chosen flights (``mcgpu_probe_xi_commit`` mode 1): ``dirs`` ``[n, 3]``, ``S`` ``[n, 4]``,
+        ``need`` / ``star`` bool ``[n]``; by the whole wave (``by_wave``) or lane by lane.  Returns the per-lane results after
+        every round: ``dict(row=[n, rowf])`` or ``dict(itheta=[n, nRT], cosw=..., sinw=...)`` (the slots' 8 bytes as float64,
+        with Stokes tracking)."""
+        T = grid_blocks * block_threads
+        d, s = _a(dirs, np.float64), _a(S, np.float64)
+        n = d.shape[0]
+        u, v, rw, m = _a(rt_u, np.float64), _a(rt_v, np.float64), _a(rt_w, np.float64), _a(mu, np.float32)
+        nRT = u.size
+        assert d.shape == (n, 3) and s.shape == (n, 4) and n % T == 0 and v.size == nRT and m.ndim == 2 and m.shape[0] == 6
+        w = np.zeros((n, 4), np.int32)
+        w[:, 3] = np.asarray(star, bool).astype(np.int32) | (np.asarray(need, bool).astype(np.int32) << 1)
+        a = XiCommitProbe()
+        a.mode, a.pola, a.contrib, a.by_wave, a.with_mu, a.row = 1, int(pola), int(contrib), int(by_wave), int(with_mu), int(row)
+        a.grid_blocks, a.block_threads, a.n_rounds, a.nRT, a.RT_n_incl, a.nang = grid_blocks, block_threads, n // T, nRT, rw.size, m.shape[1] - 1
+        a.where, a.dir, a.S, a.mu = w.ctypes.data, d.ctypes.data, s.ctypes.data, m.ctypes.data
+        a.rt_u, a.rt_v, a.rt_w = u.ctypes.data, v.ctypes.data, rw.ctypes.data
+        out = {}
+        if row:
+            lay = xi32_layout(nRT, pola, contrib)
+            rowf = (nRT * (4 if pola else 1) + 3) // 4 * 4 if lay["split"] else lay["binf"]
+            out["row"] = np.zeros((n, rowf), np.float32)
+            a.dump_row = out["row"].ctypes.data
+        else:
+            out["itheta"] = np.zeros((n, nRT), np.int32)
+            a.dump_itheta = out["itheta"].ctypes.data
+            if pola:
+                out["cosw"], out["sinw"] = np.zeros((n, nRT), np.float64), np.zeros((n, nRT), np.float64)
+                a.dump_cosw, a.dump_sinw = out["cosw"].ctypes.data, out["sinw"].ctypes.data
+        self._chk(self.lib.mcgpu_probe_xi_commit(self.ctx, C.byref(a)), "mcgpu_probe_xi_commit")
+        return out
 
     def xi_log_sentinel(self, n_bins):
         """The key of the sorted log's unused entries for ``n_bins`` sub-bins, as the commit pass computes it."""
