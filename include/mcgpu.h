@@ -227,6 +227,11 @@ int mcgpu_set_midplane_snap(mcgpu_ctx *ctx, int on);
  *                      and the deposit; the private grid gains a halo) unless the disk's midplane is optically
  *                      thick, where the records that the halo displaces matter more; 1 = padded; 2 = plain.
  *                      The same packets and deposits either way.
+ *   "fly_stay"     padded 2D role kernels (see "cell_key"; the plain ones run a full round at every visit): how often a flying wave runs a full scheduling round (ring counts, role decision)
+ *                      when it comes back to the rings for new flights.  0 (default) = automatic; 1 = at every visit;
+ *                      N > 1 = up to N - 1 lean re-entries (refill and back into the crossing loop; a stop, a hand-over
+ *                      or a demotion to server still ends the stay at once) between two full rounds.  The same packets
+ *                      and deposits whatever the value; only which wave runs a packet, and when, changes.
  *   "crossing"     0 (default) = the reference's crossing arithmetic everywhere (cross_cylindrical_cell,
  *                      cylindrical_grid.f90:918-1175: golden walks bit for bit, packets equal to the CPU
  *                      restatement's one for one); 1 = 2D grids without dark zone / random walk / dust
@@ -250,6 +255,7 @@ int mcgpu_set_midplane_snap(mcgpu_ctx *ctx, int on);
 int mcgpu_set_option(mcgpu_ctx *ctx, const char *name, int value);
 /* Diagnostics of the last launches: "bin_buckets", "bin_log_blocks", "bin_chunks",
  * "bin_deposits_per_packet", "bin_overflow_blocks", "bin_drained_records", "tail_threshold", "tau_midplane",
+ * "fly_stay" (what the last thermal launch's kernel ran with; 1 where that kernel takes no lean re-entries),
  * "tail_ms", "longest_packet_events" / _crossings / _scatterings / _absorptions / _walks / _steps, and of the last
  * launch's tail: "tail_where" (0: it had none, 1: k_tail finished it, 2: the host threads did), "tail_host_ms",
  * "tail_host_packets", "tail_host_threads", "tail_host_events"; of the last mcgpu_run_mono's commit passes:

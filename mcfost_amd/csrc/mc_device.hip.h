@@ -320,6 +320,10 @@ struct RunArgs {
   unsigned int* tail_done;          // packets k_tail has finished
   void* tail_out;                   // [tail_host_max] records (Rec<POLA>)
   unsigned int* tail_out_n;
+  // the 2D role kernels (mc_roles.hip.h, "Lean re-entry"): a flying wave makes up to fly_stay - 1 visits of the rings without
+  // a full scheduling round between two full rounds; <= 1: a full round at every visit (option "fly_stay", resolved by the launcher)
+  // (behind everything else: the kernels that never read it keep their argument layout)
+  int fly_stay;
 };
 
 // ---------------------------------------------------------------------------

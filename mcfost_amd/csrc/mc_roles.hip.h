@@ -1227,7 +1227,58 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
   RQ_DIAG(unsigned int d_srv_lanes = 0, d_srv_int = 0, d_emit = 0;)
   RQ_DIAG(unsigned int d_emit_rounds = 0, d_exit_rounds = 0, d_exit = 0, d_int_rounds = 0, d_first_rounds = 0, d_first = 0;)
 
+  // Lean re-entry (the padded 2D kernels' flying waves).  A flying wave comes back from its crossing loop every fly_iters
+  // crossings to swap its stopped packets for flights.  None of what a full round decides can change for it in between: it
+  // owns no record, it is no server, so it flies -- unless the launch stops, the workgroup hands over or wave 0 has made it
+  // a server.  So up to A.fly_stay - 1 times in a row such a wave asks only that (abort_flag and n_srv, two loads of the one control block)
+  // and goes straight to the refill below: no ring counts, no role decision.  Everything else of the round -- the refill,
+  // idle_f, the beat, the loop and its commits, n_pending, the fold clock -- is the one code that every round runs.
+  // Anything else at the control word, no flight after the refill, or the cap: the next round is a full one, so a
+  // hand-over (abort_flag 2) or a demotion is seen at the very next visit.  Liveness is the full rounds' (below): a lean
+  // round holds and puts down packets exactly as a full round of a wave that prefers to fly and holds packets does.
+  // The padded instantiations only -- the launcher's choice wherever the midplane is not optically thick, i.e. where
+  // flights are a packet's life.  The plain ones serve thick disks, whose time is the servers': the same change compiled
+  // into k_thermal_roles_tail<true,false,true,false,false> cost ref4.1 2D 4-5 % through the registers alone, with
+  // "fly_stay" = 1, so they keep the former round, statement for statement.  And one padded
+  // instantiation, k_thermal_roles_tail<false,false,true,true,true> -- the walk, handing over -- then reloads a spilled
+  // flight constant from scratch inside its flying loop: it keeps the former round too, as the DARK kernels keep forming
+  // the wall.
+  // (That carve-out is this compiler's register allocation, not a property of the code: after a change to roles_body or a
+  // new compiler look at every 2D instantiation's flying loop again -- tools/loop_mix.py --kernel <mangled name>, VMEM in
+  // the common path must stay at 1, with a dark zone 2 -- and drop or move it.)
+  // MCGPU_LEAN_PLAIN (the one-lane emulation of tests/test_fly_stay_emulated.py): the plain 2D instantiations take lean
+  // re-entries too, so that the schedule's logic runs on the host.
+#ifndef MCGPU_LEAN_PLAIN
+#define MCGPU_LEAN_PLAIN 0
+#endif
+#ifndef MCGPU_LEAN_TEST_HOOK   // (the same test counts the lean rounds it ran)
+#define MCGPU_LEAN_TEST_HOOK(taken)
+#endif
+  constexpr bool LEAN = (PAD || (MCGPU_LEAN_PLAIN && !PARAM && !VORO && !L3D && !VAR)) && !(CARRY && MRW && PAD && !POLA && !DARK);
+  int lean_left = 0;  // lean re-entries this wave may still make before its next full round
+  // (the wave's number as a scalar, formed where it is asked for: the role and what hangs on it -- serve, lean, lean_left --
+  // are then wave-uniform to the compiler and live in scalar registers.  The kernel has none to spare, neither vector nor
+  // scalar -- spilled scalars take vector lanes -- which is also why the cap is read from A where it is needed.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RQ_WAVE_S() __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))
+#else
+#define RQ_WAVE_S() wave
+#endif
+  // the partial folds' clock: rounds until this wave's next fold (every flush_every-th round, lean or full)
+  int fold_in = A.flush_every;
+
   for (int ep = 0;; ++ep) {
+    int finished = 0;  // packets this lane finished in this round
+    bool prefer_server = false, can_emit = false, serve = false;
+    bool lean = false;
+    if (LEAN && lean_left > 0) {
+      --lean_left;
+      const int stop_now = rq_ld(&Q->abort_flag), srv_now = rq_ld(&Q->n_srv);
+      lean = stop_now == 0 && RQ_WAVE_S() >= srv_now;
+      MCGPU_LEAN_TEST_HOOK(lean);
+    }
+    if (!lean) {
+    lean_left = 0;
     const int stop_flag = rq_ld(&Q->abort_flag);   // 1: error, 2 (CARRY): hand the packets over
     if (stop_flag == 1) break;
     if (CARRY && carry_out && wave == 0 && lane == 0 && stop_flag == 0) {
@@ -1235,25 +1286,26 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
       // counter has run out (seen by an emission, or looked up every 16 rounds: a workgroup whose records are full of
       // long flights emits nothing for a while) and (tail_threshold > 0: the launch's last packets go to the tail
       // kernel) no more than that many packets are left here; tail_threshold <= 0: at once (a chunk of a binned run).
-      if ((ep & 15) == 15 && !rq_ld(&Q->ids_done) &&
+      // (LEAN, no server at all -- n_srv_pref = 0, the emulation's one wave: wave 0 flies and re-enters, its full rounds
+      // can keep one residue of 16 for ever: it then looks the counter up in each of them)
+      if (((ep & 15) == 15 || (LEAN && rq_ld(&Q->n_srv) == 0)) && !rq_ld(&Q->ids_done) &&
           __hip_atomic_load(A.next_packet, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_items) rq_st(&Q->ids_done, 1);
       if (rq_ld(&Q->ids_done) && (A.tail_threshold <= 0 || rq_ld(&Q->n_pending) <= A.tail_threshold)) atomicCAS(&Q->abort_flag, 0, 2);
     }
     if (CARRY && stop_flag == 2) { suspended = true; break; }  // (the hand-over itself: behind the loop)
-    int finished = 0;  // packets this lane finished in this round
 
     // ---- which role this round -----------------------------------------------------------------------
     const bool any_owned = __ballot(rid >= 0) != 0ull;
     const bool any_held = __ballot(rid < 0 && st != S_EMIT) != 0ull;
     const int fly_n = rq_count(Q, RQ_FLY), srv_n = rq_count(Q, RQ_SRV);
     // (new packets leave free records for the flyers' stopped packets)
-    const bool can_emit = !no_more_ids && fly_n <= emit_qmax && rq_count(Q, RQ_FREE) > free_reserve;
+    can_emit = !no_more_ids && fly_n <= emit_qmax && rq_count(Q, RQ_FREE) > free_reserve;
     // Which waves serve: waves [0, n_srv).  The share of serving work depends on the model (Pascucci: 0.15
     // interactions per packet, ref4.1: 11), so wave 0 adapts n_srv every few of its rounds to what the two kinds of
     // waves could not fill since the last time: lanes of flying waves left without a flight (the servers do not
     // produce flights fast enough: one more server) against lanes of serving waves left without a packet (one fewer).
     const int n_srv_now = rq_ld(&Q->n_srv);
-    const bool prefer_server = wave < n_srv_now;
+    prefer_server = (LEAN ? RQ_WAVE_S() : wave) < n_srv_now;
     if (adapt && wave == 0 && lane == 0) {
       const int cd = rq_ld(&Q->cooldown);
       if (cd > 0) rq_st(&Q->cooldown, cd - 1);
@@ -1269,7 +1321,6 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
     // below): whatever the others hold, somebody always empties the SRV ring, which turns waiting packets into FLY
     // records or free records.  A flying wave that becomes a server drains first (no new flights; its flights go
     // to free records as they become available).
-    bool serve;
     if (prefer_server) {
       serve = !any_held;
     } else if (any_owned) {
@@ -1285,6 +1336,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
     } else {
       serve = (fly_n == 0) && ((srv_n > 0) || can_emit);
     }
+    }  // (a lean re-entry: serve = false, no server, nothing owned)
 
 #if defined(__HIP_DEVICE_COMPILE__) && defined(MCGPU_PRIO_SERVE)   // (A/B builds: the issue priority of a wave by its role)
     if (serve) __builtin_amdgcn_s_setprio(MCGPU_PRIO_SERVE); else __builtin_amdgcn_s_setprio(MCGPU_PRIO_FLY);
@@ -1338,10 +1390,12 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
           st = S_EMIT;
         }
       }
-      {
+      if (!LEAN || draining) {   // (only a draining wave puts flights down)
         const bool was_flight = rout >= 0 && (recs[rout].flags & ST_MASK) == S_FLIGHT;
         rq_push(Q, rings, RQ_SRV, lane, rout >= 0 && !was_flight, rout);
         rq_push(Q, rings, RQ_FLY, lane, rout >= 0 && was_flight, rout);
+      } else {
+        rq_push(Q, rings, RQ_SRV, lane, rout >= 0, rout);
       }
       rq_push(Q, rings, RQ_FREE, lane, rin >= 0 && rout != rin, rin);  // loaded, not swapped: the record is free again
 
@@ -1350,6 +1404,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         if (n_idle > 0 && lane == 0) atomicAdd(&Q->idle_f, n_idle);
       }
       if (__ballot(st == S_FLIGHT) == 0ull) {
+        lean_left = 0;  // (nothing to fly: the role is decided anew)
         if (__ballot(st != S_EMIT) == 0ull && rq_ld(&Q->ids_done) && rq_ld(&Q->n_pending) == 0) break;
         __builtin_amdgcn_s_sleep(16);  // nothing to fly (or no record for a stopped packet): wait for the others
         { const int b = rq_ld(&Q->beat); if (b != last_beat) { last_beat = b; idle_spins = 0; } }
@@ -1357,6 +1412,8 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
       } else {
         idle_spins = 0;
         if (lane == 0) atomicAdd(&Q->beat, 1);
+        // (a full round opens the next stay; a draining wave is a server, whom the control word sends to a full round anyway)
+        if (LEAN && !lean) lean_left = A.fly_stay > 1 ? A.fly_stay - 1 : 0;
         RQ_DIAG(if (lane == 0) d_fly_rounds++;)
         F.st = st;
         FlightParam FP;
@@ -1745,8 +1802,11 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         if (e != 0.0) atomic_add_f64(&A.E_abs[t - 1], e);
       }
     }
-    if (LDSE && ((ep + 1) % A.flush_every) == 0) {  // barrier-free partial fold (see thermal_body)
+    // barrier-free partial fold (see thermal_body): in every flush_every-th round of this wave, lean or full -- counted
+    // down, so that only the round that folds divides
+    if (LDSE && (LEAN ? --fold_in == 0 : ((ep + 1) % A.flush_every) == 0)) {
       const int n_waves = (blockDim.x + 63) >> 6;
+      fold_in = A.flush_every;
       const int slice = (wave + (ep + 1) / A.flush_every) % n_waves;
       if (PAD) {  // (by rows; a halo slot is nobody's cell and keeps what it collected)
         pad_fold_rows(n_rad, nz, n_waves, slice, lane, [&](int K, int ic) {
@@ -1765,6 +1825,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
       }
     }
   }
+#undef RQ_WAVE_S
 
   if (CARRY && suspended) {
     // ---- end of a chunk: what this wave holds goes to carry_out (see "Chunks without tails") -----------------

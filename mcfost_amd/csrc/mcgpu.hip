@@ -194,7 +194,9 @@ struct mcgpu_ctx {
   int opt_schedule = 0;     // 0 = automatic (waves with roles where the queues fit), 1 = single-role kernel
   int opt_speculation = 1;  // SED mode: commit most of every stream before the scout pass
   int opt_cache_log_slots = 13;  // Voronoi deposit cache: 2^13 slots = 96 KB of LDS
-  int opt_cell_key = 0;          // the 2D role kernels' cell key: 0 = automatic (padded unless the midplane is optically thick), 1 = padded, 2 = plain
+  int opt_fly_stay = 0;          // the 2D role kernels' flying waves: 0 = automatic, 1 = a full round at every visit of the rings, N > 1 = up to N - 1 lean re-entries between full rounds
+  int last_fly_stay = 1;         // the last thermal launch: RunArgs::fly_stay where its kernel takes lean re-entries (mc_roles.hip.h, LEAN), else 1
+  int opt_cell_key = 0;        // the 2D role kernels' cell key: 0 = automatic (padded unless the midplane is optically thick), 1 = padded, 2 = plain
   int opt_crossing = 0;          // 1: the flight-parametric 2D crossing in the role kernel's flying waves (statistical parity only)
   int opt_pool_log_rec = 12;     // Voronoi pool schedule: 2^12 packet records per workgroup (mc_voronoi_pool.hip.h)
   int opt_nlte_stats = 0;        // 1: a non-LTE launch counts the events its waves serve (mcgpu_get_info "nlte_events" / "nlte_visits")
@@ -647,6 +649,7 @@ extern "C" int mcgpu_set_option(mcgpu_ctx* ctx, const char* name, int value) {
   else if (!strcmp(name, "schedule")) { if (value < 0 || value > 3) return fail(ctx, MCGPU_ERR_ARG, "schedule: 0, 1, 2 or 3"); ctx->opt_schedule = value; }
   else if (!strcmp(name, "speculation")) ctx->opt_speculation = value ? 1 : 0;
   else if (!strcmp(name, "cell_key")) { if (value < 0 || value > 2) return fail(ctx, MCGPU_ERR_ARG, "cell_key: 0, 1 or 2"); ctx->opt_cell_key = value; }
+  else if (!strcmp(name, "fly_stay")) { if (value < 0 || value > (1 << 20)) return fail(ctx, MCGPU_ERR_ARG, "fly_stay: 0 (automatic), 1, or N > 1"); ctx->opt_fly_stay = value; }
   else if (!strcmp(name, "crossing")) { if (value < 0 || value > 1) return fail(ctx, MCGPU_ERR_ARG, "crossing: 0 or 1"); ctx->opt_crossing = value; }
   else if (!strcmp(name, "voronoi_pool_log_records")) { if (value < 6 || value > VP_MAX_LOG_REC) return fail(ctx, MCGPU_ERR_ARG, "voronoi_pool_log_records: 6..12"); ctx->opt_pool_log_rec = value; }
   else if (!strcmp(name, "voronoi_cache_log_slots")) { if (value < 6 || value > 13) return fail(ctx, MCGPU_ERR_ARG, "voronoi_cache_log_slots: 6..13"); ctx->opt_cache_log_slots = value; }
@@ -665,6 +668,7 @@ extern "C" int mcgpu_get_info(mcgpu_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "bin_chunks")) *value = ctx->bin_chunks;
   else if (!strcmp(name, "bin_deposits_per_packet")) *value = ctx->bin_dep_per_packet;
   else if (!strcmp(name, "tail_threshold")) *value = tail_threshold(ctx);
+  else if (!strcmp(name, "fly_stay")) *value = ctx->last_fly_stay;   // what the last thermal launch's kernel ran with (1: it takes no lean re-entries)
   else if (!strcmp(name, "nlte_events") || !strcmp(name, "nlte_visits")) {   // the last non-LTE launch: absorptions served by
     unsigned long long v[2] = {0ull, 0ull};                                  // whole waves, and wave visits that served any
     if (ctx->nl.d_stats) {
@@ -1765,6 +1769,13 @@ static int launch_mega(mcgpu_ctx* ctx, const RunArgs& A, bool use_lds, int grid_
       // 2D grids: the launch's last packets go to the tail kernel (one packet per wave, mc_tail.hip.h) once a
       // workgroup has no more than opt_tail of them left
       RunArgs At = A;
+      // visits of the rings that a flying wave makes per full scheduling round (mc_roles.hip.h, "Lean re-entry"; 2D, not the
+      // flight-parametric form).  Automatic: 16, by argument and not swept (measured: 16 against 1) -- a full round's extra cost is then a sixteenth of what it was, and a wave
+      // still decides its role anew twice per Pascucci packet's worth of crossings
+      At.fly_stay = tune("MCGPU_FLY_STAY", ctx->opt_fly_stay > 0 ? ctx->opt_fly_stay : (ctx->tau_midplane > 1000.0 ? 1 : 16), 1, 1 << 20);
+      // (the instantiations that take lean re-entries: roles_body's LEAN)
+      const bool lean_kernel = pad && !param && !(tail_thr > 0 && M.mrw && !pola && !dark);
+      ctx->last_fly_stay = lean_kernel ? At.fly_stay : 1;
       const bool tail = !l3d && tail_thr > 0;
       if (tail) {
         int rc = carry_prepare(ctx, rblocks, n_rec, rthreads);
@@ -2160,6 +2171,7 @@ extern "C" int mcgpu_launch_thermal(mcgpu_ctx* ctx, const mcgpu_run_opts* o) {
   HIPCHK(hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream));
   ctx->tail_launched = false;
   ctx->tail_on_host = false;
+  ctx->last_fly_stay = 1;
   RunArgs A;
   std::memset(&A, 0, sizeof(A));
   A.seed = o->seed; A.first_packet = o->first_packet; A.n_packets = o->n_packets;
