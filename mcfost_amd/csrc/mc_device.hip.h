@@ -111,6 +111,17 @@ __device__ __forceinline__ int f64_to_i32_sat(double x) {
   return r;
 #endif
 }
+// |a - b| + 1 on unsigned integers: one v_sad_u32 (the compiler expands __usad into four instructions here, and has no
+// __builtin_amdgcn_ for it); the host emulation writes the same answer out.
+__device__ __forceinline__ unsigned int sad_plus1_u32(unsigned int a, unsigned int b) {
+#ifdef MCGPU_LANE_EMULATION
+  return (a > b ? a - b : b - a) + 1u;
+#else
+  unsigned int r;
+  asm("v_sad_u32 %0, %1, %2, 1" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+#endif
+}
 // ... without the last correction step: within a few units in the last place (the flight-parametric crossing, which
 // makes no claim on the reference's last bits)
 __device__ __forceinline__ double sqrt_fast_nonneg(double x) {

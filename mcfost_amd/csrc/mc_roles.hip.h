@@ -596,6 +596,35 @@ __device__ __forceinline__ int fly_step_2d(const Lds& T, const DevModel& M, cons
 // s1 == 0, bit 1: t < 0, bit 2: z1 == 0 (for tests/emu/emu_fly_visit.cpp; the kernels do not read it).
 // WALL: section 2 takes the wall ahead from the flight (p.zw, the cell's WallRec for this crossing's `away`) instead of
 // forming it; WALL = false is the specification of that form (tests/emu/emu_fly_wall.cpp walks both).
+// The crossing's bookkeeping as fly_geom_2d<WALL = true> forms it: three pieces that cost the specification's statements
+// 6, 7 and 2 vector instructions and these 4, 3 and 1 (tests/emu/emu_fly_geom.cpp holds each against the specification).
+//
+// The wall ahead on the packet's side of the midplane: zl = (z0 < 0.0) ? -zw : zw as one mask and one exclusive or on the
+// high word -- z0's sign bit goes into the wall.  The two differ for z0 = -0.0 alone (no compare sees that sign); there
+// dz = w * z0 == 0.0, so section 2 replaces the time by 1e10 and gates the fix-up bit, whatever zl was.  (The sign cannot
+// wait until after the subtraction, as +-(zw - |z0|): a packet ON the wall gives +0.0 - the specification's -zw - z0 is
+// (-a) + a = +0.0 - and the sign would turn that into -0.0.)
+__device__ __forceinline__ double pad_wall_side(double zw, double z0) {
+  return __longlong_as_double(__double_as_longlong(zw) ^ (__double_as_longlong(z0) & (long long)0x8000000000000000ull));
+}
+// The layer behind the vertical wall: zj0 + delta_zj with delta_zj = away ? (top ? 0 : 1) : (zj0 == 1 ? 1 : -1), in closed
+// form min(|zj0 + (away ? 1 : -1) - 1| + 1, nz + 1) = min(|zj0 - (away ? 0 : 2)| + 1, nz + 1).  Since zj0 >= 1: down from
+// zj0 = 1 the difference is 1 and the layer 2, the far side of the mirror cell (the specification's + 1); up from nz + 1 the
+// minimum holds the packet in that row (its 0); everywhere else zj0 +- 1.  `away` is section 2's compare, not dz's sign.
+__device__ __forceinline__ int fly_layer_step(int nz, int zj0, bool away) {
+  const unsigned int zv = sad_plus1_u32((unsigned int)zj0, away ? 0u : 2u);
+  return (int)(zv < (unsigned int)(nz + 1) ? zv : (unsigned int)(nz + 1));
+}
+// The row of radial index ri (0 <= ri <= n_rad + 2: 24 bits hold it) at a 32-bit offset: one 24-bit multiply-add on the
+// table's address instead of a 64-bit one behind a move.
+__device__ __forceinline__ const RowT& fly_row(const Lds& T, int ri) {
+#ifdef MCGPU_LANE_EMULATION
+  return T.row[ri];
+#else
+  return *reinterpret_cast<const RowT*>(reinterpret_cast<const char*>(T.row) + __umul24((unsigned int)ri, (unsigned int)sizeof(RowT)));
+#endif
+}
+
 template <bool WALL = false>
 __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, const Flight& p, double& l_out, double& z1_out,
                                             int& ri1_out, int& zj1_out) {
@@ -605,7 +634,7 @@ __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, cons
   const double x0 = p.x, y0 = p.y, z0 = p.z, u = p.u, v = p.v, w = p.w;
   const bool top = (zj0 == nz + 1);
   const bool hole = (ri0 == 0);
-  const RowT& R0 = T.row[ri0];
+  const RowT& R0 = WALL ? fly_row(T, ri0) : T.row[ri0];
   int fix = 0;
 
   // 1) radial wall
@@ -631,9 +660,9 @@ __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, cons
   const bool away = dz > 0.0;
   double zl;
   if (WALL) {
-    // (the record's wall carries everything but the side of the midplane the packet is on; the compare, not z0's sign
-    // bit: a stopping point can be -0.0)
-    zl = (z0 < 0.0) ? -p.zw : p.zw;
+    // (the record's wall carries everything but the side of the midplane the packet is on: zl = (z0 < 0.0) ? -p.zw : p.zw,
+    // see pad_wall_side for a stopping point at -0.0)
+    zl = pad_wall_side(p.zw, z0);
   } else {
     const bool flip = !away && (zj0 == 1);
     const int jm = away ? zj0 : (zj0 == 1 ? 1 : zj0 - 1);
@@ -655,7 +684,7 @@ __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, cons
   const double l = fmin(s, t);
   double z1 = nd_add(z0, nd_mul(l, w));
   const int ri1 = rad ? ri0 + delta_rad : ri0;
-  const double qd = fabs(z1) * T.row[ri1].rzn;
+  const double qd = fabs(z1) * (WALL ? fly_row(T, ri1) : T.row[ri1]).rzn;
   const double fl = floor(qd);
   // (the minimum on the integers, behind a conversion that saturates: for fl >= 0 the same zj as fly_step_2d's minimum on
   // the doubles; a NaN, which only a broken state brings here, gives zj = 1 where that gives nz + 1)
@@ -668,7 +697,11 @@ __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, cons
     zjr = zq > nz ? nz + 1 : zq;
   }
   zjr = (ri1 > n_rad) ? zj0 : zjr;
-  zj1_out = rad ? zjr : zj0 + delta_zj;
+  // (formed in front of the select: a named instruction inside one arm of it would become a branch)
+  if (WALL) {
+    const int zv = fly_layer_step(nz, zj0, away);
+    zj1_out = rad ? zjr : zv;
+  } else zj1_out = rad ? zjr : zj0 + delta_zj;
   fix |= (z1 == 0.0) ? 4 : 0;
   z1 = (z1 == 0.0) ? GRID_PREC : z1;
   l_out = l; z1_out = z1; ri1_out = ri1;
@@ -725,6 +758,9 @@ __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& 
         p.y = __builtin_fma(lc, v, y0);
         p.z = __builtin_fma(lc, w, z0);
         p.st = S_INTERACT;
+        // (the flight is over and its next one loads a wall of its own: saying so here, on the rare side, leaves the wall
+        // dead behind section 2 on every path, and the sign goes into its register in place)
+        if (WALL) p.zw = 0.0;
       } else {
         if (dep) deposit<LDSE>(A.E_abs, E_lds, ic, p.kab * l * p.S0);  // save_radiation_field
         const bool next_real = PAD || (((unsigned)(ri1 - 1) < (unsigned)n_rad) & ((unsigned)(zj1 - 1) < (unsigned)nz));
@@ -1510,7 +1546,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
             if ((fl_c & ST_MASK) == S_EMIT) pid = ((unsigned long long)Rc.p_hi << 32) | Rc.p_lo;
             else { rec_copy(&recs[r], &Rc); rid = r; st = fl_c & ST_MASK; fresh = false; }
           }
-          RQ_DIAG(if (lane == 0 && __ballot(fresh) != 0ull) d_emit_rounds++;)
+          RQ_DIAG({ const unsigned long long any_ = __ballot(fresh); if (lane == 0 && any_ != 0ull) d_emit_rounds++; })   // (the vote of the whole wave, taken in front of lane 0's branch)
           if (fresh) {
             rid = r;
             Rec<POLA>& R = recs[rid];
@@ -1582,7 +1618,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         float rand2 = 0.0f;
         bool scat = false;
         const bool inter = rid >= 0 && st == S_INTERACT;
-        RQ_DIAG(if (lane == 0 && __ballot(inter) != 0ull) d_int_rounds++;)
+        RQ_DIAG({ const unsigned long long any_ = __ballot(inter); if (lane == 0 && any_ != 0ull) d_int_rounds++; })   // (the vote of the whole wave, taken in front of lane 0's branch)
         if (inter) {
           Rec<POLA>& R = recs[rid];
           Rng rng;
@@ -1756,7 +1792,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         }
         RQ_PHASE_END();
         // ---- packets that left the grid: capteur (output.f90:294-597) --------------------------------------
-        RQ_DIAG(if (lane == 0 && __ballot(rid >= 0 && st == S_EXITED) != 0ull) d_exit_rounds++;)
+        RQ_DIAG({ const unsigned long long any_ = __ballot(rid >= 0 && st == S_EXITED); if (lane == 0 && any_ != 0ull) d_exit_rounds++; })   // (the vote of the whole wave, taken in front of lane 0's branch)
         if (rid >= 0 && st == S_EXITED) {
           RQ_DIAG(d_exit++;)
           const Rec<POLA>& R = recs[rid];
