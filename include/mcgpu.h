@@ -256,6 +256,8 @@ int mcgpu_set_option(mcgpu_ctx *ctx, const char *name, int value);
 /* Diagnostics of the last launches: "bin_buckets", "bin_log_blocks", "bin_chunks",
  * "bin_deposits_per_packet", "bin_overflow_blocks", "bin_drained_records", "tail_threshold", "tau_midplane",
  * "fly_stay" (what the last thermal launch's kernel ran with; 1 where that kernel takes no lean re-entries),
+ * "serve_fused" (1 where the last thermal launch's kernel was a padded 2D role kernel, whose serving lanes bin an exited
+ * packet and emit the next one into the same record in one round; 0 for every other kernel.  The same packets either way),
  * "tail_ms", "longest_packet_events" / _crossings / _scatterings / _absorptions / _walks / _steps, and of the last
  * launch's tail: "tail_where" (0: it had none, 1: k_tail finished it, 2: the host threads did), "tail_host_ms",
  * "tail_host_packets", "tail_host_threads", "tail_host_events"; of the last mcgpu_run_mono's commit passes:

@@ -56,7 +56,29 @@
 #define RQ_DIAG(...)
 #endif
 
+#ifndef MCGPU_SERVE_FUSED  // 1: a serving lane of the padded 2D kernels bins its exit and emits into the same record in one
+#define MCGPU_SERVE_FUSED 1  // round (roles_body, FUSED); 0: the former order of the phases (A/B builds)
+#endif
+#ifndef MCGPU_SERVE_FUSED_PLAIN  // (the one-lane emulation: the plain 2D instantiations run the fused round)
+#define MCGPU_SERVE_FUSED_PLAIN 0
+#endif
+#ifndef MCGPU_SERVE_FUSED_TEST_HOOK   // (the same emulation counts the records it reused and the exits it held)
+#define MCGPU_SERVE_FUSED_TEST_HOOK(reused, held)
+#endif
+#ifndef MCGPU_SERVE_FUSED_HAND_HOOK   // (... and the held exits that a hand-over wrote out)
+#define MCGPU_SERVE_FUSED_HAND_HOOK(handed)
+#endif
+
 namespace mcgpu {
+
+// Whether an instantiation of roles_body with the padded key (`pad`: its PAD) runs the fused serving round; the launcher
+// reports it.  Three padded instantiations keep the former round: with the fused one their flying loop gains a reload from
+// scratch (this compiler's register allocation, as for LEAN: look again after a change to roles_body or a new compiler,
+// tools/loop_mix.py --kernel <mangled name>) -- k_thermal_roles<false,*,true,true,false,true> (a dark zone, no walk, no
+// hand-over) and k_thermal_roles_tail<false,true,true,true,true> (no Stokes tracking, a dark zone, the walk, handing over).
+constexpr bool roles_serve_fused(bool pad, bool pola, bool dark, bool mrw, bool carry) {
+  return pad && MCGPU_SERVE_FUSED != 0 && !(dark && !mrw && !carry) && !(carry && !pola && dark && mrw);
+}
 
 constexpr int RQ_CAP = 512;          // entries per ring (power of two, >= records per workgroup)
 constexpr int RQ_MIN_REC = 96;       // fewer records than this: the single-role kernel runs instead
@@ -1153,6 +1175,27 @@ __device__ inline int voro_roles_cross(const Lds& T, const DevModel& M, const Ru
 #define RQ_PHASE_END()
 #endif
 
+// The serving round's capteur phase (output.f90:294-597): the lanes whose record holds a packet that left the grid bin it.
+// The text of ONE phase that roles_body places by its FUSED -- behind the first crossings, where the record then goes to the
+// FREE ring (the former order, which the plain instantiations keep statement for statement), or directly behind the SRV
+// pop, where the lane keeps the record for the emission of the same round -- so an instantiation holds one inlined copy.
+#define RQ_BIN_EXITS() { \
+        RQ_DIAG({ const unsigned long long any_ = __ballot(rid >= 0 && st == S_EXITED); if (lane == 0 && any_ != 0ull) d_exit_rounds++; })   /* (the vote of the whole wave, taken in front of lane 0's branch) */ \
+        if (rid >= 0 && st == S_EXITED) { \
+          RQ_DIAG(d_exit++;) \
+          const Rec<POLA>& R = recs[rid]; \
+          const int fl = R.flags; \
+          if (!(fl & ST_ISM) ) {  /* ISM packets that were never absorbed are not binned (dust_transfer.f90:549) */ \
+            const double S[4] = {R.S[0], POLA ? R.S[POLA ? 1 : 0] : 0.0, POLA ? R.S[POLA ? 2 : 0] : 0.0, POLA ? R.S[POLA ? 3 : 0] : 0.0}; \
+            capteur<POLA>(M, A.sed, R.lambda, R.u, R.v, R.w, S, (fl & ST_STAR) != 0, (fl & ST_SCATT) != 0); \
+            c_esc++; \
+          } \
+          { const unsigned int ev = (R.pk_cross & 0x7FFFFFFFu) + R.event; ev_max = ev > ev_max ? ev : ev_max; } \
+          st = S_EMIT; \
+          finished++; \
+        } \
+      }
+
 // VORO: the same schedule on a Voronoi grid (G; L3D = true, DARK = LDSE = MRW = false): a record's ri is the packet's
 // cell, zj the cell it came from, star_key the cell of the star on its way; deposits go through the workgroup's
 // deposit cache (DepCache, 2^cache_log_ns slots behind the tables) instead of a private grid.
@@ -1238,7 +1281,8 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
   bool suspended = false;
 
   // ---- per-lane state ------------------------------------------------------------------------------------
-  // serving: rid >= 0 names the record this lane owns, st its packet's state (S_INTERACT between rounds)
+  // serving: rid >= 0 names the record this lane owns, st its packet's state (between rounds S_INTERACT, or -- the fused
+  //          serving round, see FUSED -- S_EXITED: an exit the lane bins at the top of its next serving round)
   // flying:  rid < 0 and F, bag_* hold a packet (st = S_FLIGHT, or S_INTERACT / S_EXITED once it stopped); st = S_EMIT: empty
   int rid = -1, st = S_EMIT;
   Flight F;
@@ -1292,6 +1336,27 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
 #endif
   constexpr bool LEAN = (PAD || (MCGPU_LEAN_PLAIN && !PARAM && !VORO && !L3D && !VAR)) && !(CARRY && MRW && PAD && !POLA && !DARK);
   int lean_left = 0;  // lean re-entries this wave may still make before its next full round
+  // Exit first, then emit into the same record (the padded 2D kernels' serving waves).  On a thin disk a packet is one
+  // emission, its flights and one exit, and the servers' lanes are busy with the two ends: a lane that pops an exited
+  // packet runs capteur and gives the record to the FREE ring, and some lane pops that record in a later round to emit --
+  // two owned lane-rounds, and each of the two long instruction streams (emission + first crossings, capteur) runs in
+  // about half of the rounds for half a wave (measured: profiles/r06_serve_fused_ab.log).  FUSED: capteur runs directly behind the SRV pop, the lane KEEPS its record
+  // (st = S_EMIT, rid >= 0) and the emission of the same round writes the next packet into it: no trip through the FREE
+  // ring, one lane-round for both.  A lane that may not emit (no ids left, FLY ring over emit_qmax) gives the record to
+  // the FREE ring in the push phase as before.  What becomes S_EXITED behind the capteur phase -- an emission that misses
+  // the grid, an exit within the first crossings, a flight flown in place that leaves -- stays this lane's record with
+  // that state (it is in R.flags) and is binned at the top of the lane's next serving round: between rounds an owned record
+  // is S_INTERACT or S_EXITED.  Whoever reads an owned record between rounds takes either: the give-back to the SRV ring
+  // (the next server to pop it bins it), the hand-over (the tail takes S_EXITED records as it takes them from a flyer's
+  // registers).  A wave that owns records serves in its next round or gives them back, wave 0 always serves: every held
+  // exit is binned, n_pending falls, the launch ends.  Nothing waits for anything.
+  // The padded instantiations only (thin disks, where emission and exit are the servers' work); the plain ones -- the thick
+  // disks', whose registers are balanced on a knife's edge, see LEAN -- keep the former round, statement for statement.
+  // MCGPU_SERVE_FUSED=0: the former order everywhere (A/B builds); MCGPU_SERVE_FUSED_PLAIN (the one-lane emulation of
+  // tests/test_serve_fused_emulated.py): the plain 2D instantiations run the fused round too.
+  // Three padded instantiations are carved out (roles_serve_fused: a scratch reload in their flying loop otherwise).
+  constexpr bool FUSED = roles_serve_fused(PAD, POLA, DARK, MRW, CARRY) ||
+                         (MCGPU_SERVE_FUSED != 0 && MCGPU_SERVE_FUSED_PLAIN && !PARAM && !VORO && !L3D && !VAR && !BIN);
   // (the wave's number as a scalar, formed where it is asked for: the role and what hangs on it -- serve, lean, lean_left --
   // are then wave-uniform to the compiler and live in scalar registers.  The kernel has none to spare, neither vector nor
   // scalar -- spilled scalars take vector lanes -- which is also why the cap is read from A where it is needed.)
@@ -1335,7 +1400,9 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
     const bool any_held = __ballot(rid < 0 && st != S_EMIT) != 0ull;
     const int fly_n = rq_count(Q, RQ_FLY), srv_n = rq_count(Q, RQ_SRV);
     // (new packets leave free records for the flyers' stopped packets)
-    can_emit = !no_more_ids && fly_n <= emit_qmax && rq_count(Q, RQ_FREE) > free_reserve;
+    // (FUSED: a lane that emits into the record it holds asks the FREE ring for nothing -- can_emit is then "ids left and
+    // the FLY ring not too long", and the reserve is looked at where a lane pops the FREE ring)
+    can_emit = !no_more_ids && fly_n <= emit_qmax && (FUSED || rq_count(Q, RQ_FREE) > free_reserve);
     // Which waves serve: waves [0, n_srv).  The share of serving work depends on the model (Pascucci: 0.15
     // interactions per packet, ref4.1: 11), so wave 0 adapts n_srv every few of its rounds to what the two kinds of
     // waves could not fill since the last time: lanes of flying waves left without a flight (the servers do not
@@ -1370,7 +1437,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
     } else if (any_held) {
       serve = false;
     } else {
-      serve = (fly_n == 0) && ((srv_n > 0) || can_emit);
+      serve = (fly_n == 0) && (FUSED ? ((srv_n > 0) || (can_emit && rq_count(Q, RQ_FREE) > free_reserve)) : ((srv_n > 0) || can_emit));
     }
     }  // (a lean re-entry: serve = false, no server, nothing owned)
 
@@ -1499,14 +1566,22 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
     } else {
       // ======================= SERVING =================================================================
       RQ_DIAG(if (lane == 0) d_srv_rounds++;)
+      MCGPU_SERVE_FUSED_TEST_HOOK(false, FUSED && rid >= 0 && st == S_EXITED);   // (an exit this lane held since its last round)
       // ---- lanes without a record take a packet that waits for its interaction ... ----------------------
       if (__ballot(rid < 0) != 0ull) {
         const int r = rq_pop(Q, rings, RQ_SRV, lane, rid < 0);
         if (r >= 0) { rid = r; st = recs[r].flags & ST_MASK; }  // (S_INTERACT, or S_EXITED: to be binned)
       }
-      // ---- ... or a free record for a new packet (mc_photon_loop body, dust_transfer.f90:529-541) -------
+      // ---- (FUSED) packets that left the grid: capteur, in front of the emission -- popped just now, or held since this
+      // lane's last serving round; the lane keeps rid, st = S_EMIT ---------------------------------------------------
+      if (FUSED) {
+        RQ_BIN_EXITS()
+        RQ_PHASE_END();
+      }
+      // ---- ... or a free record for a new packet (mc_photon_loop body, dust_transfer.f90:529-541); FUSED: or the
+      // record whose packet this lane has just binned, with no ring operation ---------------------------------------
       {
-        const unsigned long long mask = __ballot(rid < 0);
+        const unsigned long long mask = __ballot(FUSED ? (rid < 0 || st == S_EMIT) : rid < 0);   // (rid >= 0, S_EMIT: binned just now)
         if (mask && can_emit) {
           if (pk_next >= pk_end) {
             const int leader = __ffsll((long long)mask) - 1;
@@ -1531,8 +1606,15 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
           }
           const unsigned long long avail = pk_end - pk_next;
           const unsigned long long rank = (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
-          const int r = rq_pop(Q, rings, RQ_FREE, lane, rid < 0 && rank < avail);
-          // ids go to the lanes that got a record, in lane order
+          // (FUSED: only the lanes without a record pop the FREE ring, and only they are held back by its reserve; a lane
+          // that has just binned its packet emits into the record it holds)
+          int r_fused = -1;
+          if (FUSED) {
+            if (rq_count(Q, RQ_FREE) > free_reserve) r_fused = rq_pop(Q, rings, RQ_FREE, lane, rid < 0 && rank < avail);
+            if (rid >= 0 && st == S_EMIT && rank < avail) { r_fused = rid; MCGPU_SERVE_FUSED_TEST_HOOK(true, false); }
+          }
+          const int r = FUSED ? r_fused : rq_pop(Q, rings, RQ_FREE, lane, rid < 0 && rank < avail);
+          // ids go to the lanes that got a record (FUSED: or hold one), in lane order
           const unsigned long long got = __ballot(r >= 0);
           const unsigned long long my = pk_next + (unsigned long long)__popcll(got & ((1ull << lane) - 1ull));
           pk_next += (unsigned long long)__popcll(got);
@@ -1791,22 +1873,11 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
           }
         }
         RQ_PHASE_END();
-        // ---- packets that left the grid: capteur (output.f90:294-597) --------------------------------------
-        RQ_DIAG({ const unsigned long long any_ = __ballot(rid >= 0 && st == S_EXITED); if (lane == 0 && any_ != 0ull) d_exit_rounds++; })   // (the vote of the whole wave, taken in front of lane 0's branch)
-        if (rid >= 0 && st == S_EXITED) {
-          RQ_DIAG(d_exit++;)
-          const Rec<POLA>& R = recs[rid];
-          const int fl = R.flags;
-          if (!(fl & ST_ISM) ) {  // ISM packets that were never absorbed are not binned (dust_transfer.f90:549)
-            const double S[4] = {R.S[0], POLA ? R.S[POLA ? 1 : 0] : 0.0, POLA ? R.S[POLA ? 2 : 0] : 0.0, POLA ? R.S[POLA ? 3 : 0] : 0.0};
-            capteur<POLA>(M, A.sed, R.lambda, R.u, R.v, R.w, S, (fl & ST_STAR) != 0, (fl & ST_SCATT) != 0);
-            c_esc++;
-          }
-          { const unsigned int ev = (R.pk_cross & 0x7FFFFFFFu) + R.event; ev_max = ev > ev_max ? ev : ev_max; }
-          st = S_EMIT;
-          finished++;
-        }
-        // ---- long flights to the FLY ring, finished packets' records to the FREE ring ------------------------
+        // ---- packets that left the grid: capteur (FUSED: they stay this lane's, S_EXITED, for the top of its next
+        // serving round) ------------------------------------------------------------------------------------
+        if (!FUSED) RQ_BIN_EXITS()
+        // ---- long flights to the FLY ring, finished packets' records to the FREE ring (FUSED: also the record of a
+        // lane that binned its exit and could not emit) ------------------------------------------------------
         {
           const bool to_fly = rid >= 0 && st == S_FLIGHT, to_free = rid >= 0 && st == S_EMIT;
           rq_push(Q, rings, RQ_FLY, lane, to_fly, rid);
@@ -1886,7 +1957,8 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         R.ri = F.ri; R.zj = F.zj; R.k = F.k; R.lambda = bag_lambda; R.star_key = F.star_key;
         R.p_lo = bag_plo; R.p_hi = bag_phi; R.event = bag_event; R.pk_cross = F.pk_cross; R.tau_rand = bag_tau;
         R.flags = st | bag_fl;
-      } else if (owned) {
+      } else if (owned) {   // (S_INTERACT, or -- FUSED -- an exit that waits for its capteur: the tail bins it)
+        MCGPU_SERVE_FUSED_HAND_HOOK(FUSED && st == S_EXITED);
         recs[rid].flags = (recs[rid].flags & ~ST_MASK) | st;
         rec_copy(&carry_out[at++], &recs[rid]);
       }

@@ -196,6 +196,7 @@ struct mcgpu_ctx {
   int opt_cache_log_slots = 13;  // Voronoi deposit cache: 2^13 slots = 96 KB of LDS
   int opt_fly_stay = 0;          // the 2D role kernels' flying waves: 0 = automatic, 1 = a full round at every visit of the rings, N > 1 = up to N - 1 lean re-entries between full rounds
   int last_fly_stay = 1;         // the last thermal launch: RunArgs::fly_stay where its kernel takes lean re-entries (mc_roles.hip.h, LEAN), else 1
+  int last_serve_fused = 0;      // the last thermal launch: 1 where its kernel's serving lanes bin an exit and emit into the same record in one round (mc_roles.hip.h, FUSED)
   int opt_cell_key = 0;        // the 2D role kernels' cell key: 0 = automatic (padded unless the midplane is optically thick), 1 = padded, 2 = plain
   int opt_crossing = 0;          // 1: the flight-parametric 2D crossing in the role kernel's flying waves (statistical parity only)
   int opt_pool_log_rec = 12;     // Voronoi pool schedule: 2^12 packet records per workgroup (mc_voronoi_pool.hip.h)
@@ -669,6 +670,7 @@ extern "C" int mcgpu_get_info(mcgpu_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "bin_deposits_per_packet")) *value = ctx->bin_dep_per_packet;
   else if (!strcmp(name, "tail_threshold")) *value = tail_threshold(ctx);
   else if (!strcmp(name, "fly_stay")) *value = ctx->last_fly_stay;   // what the last thermal launch's kernel ran with (1: it takes no lean re-entries)
+  else if (!strcmp(name, "serve_fused")) *value = ctx->last_serve_fused;   // whether the last thermal launch's kernel ran the fused serving round
   else if (!strcmp(name, "nlte_events") || !strcmp(name, "nlte_visits")) {   // the last non-LTE launch: absorptions served by
     unsigned long long v[2] = {0ull, 0ull};                                  // whole waves, and wave visits that served any
     if (ctx->nl.d_stats) {
@@ -1776,6 +1778,7 @@ static int launch_mega(mcgpu_ctx* ctx, const RunArgs& A, bool use_lds, int grid_
       // (the instantiations that take lean re-entries: roles_body's LEAN)
       const bool lean_kernel = pad && !param && !(tail_thr > 0 && M.mrw && !pola && !dark);
       ctx->last_fly_stay = lean_kernel ? At.fly_stay : 1;
+      ctx->last_serve_fused = roles_serve_fused(pad && !param, pola, dark, M.mrw != 0, !l3d && tail_thr > 0) ? 1 : 0;   // (roles_body's FUSED)
       const bool tail = !l3d && tail_thr > 0;
       if (tail) {
         int rc = carry_prepare(ctx, rblocks, n_rec, rthreads);
@@ -2172,6 +2175,7 @@ extern "C" int mcgpu_launch_thermal(mcgpu_ctx* ctx, const mcgpu_run_opts* o) {
   ctx->tail_launched = false;
   ctx->tail_on_host = false;
   ctx->last_fly_stay = 1;
+  ctx->last_serve_fused = 0;
   RunArgs A;
   std::memset(&A, 0, sizeof(A));
   A.seed = o->seed; A.first_packet = o->first_packet; A.n_packets = o->n_packets;
