@@ -657,6 +657,13 @@ int mcgpu_probe_philox(mcgpu_ctx *ctx, const uint32_t ctr[4],
                        const uint32_t key[2], uint32_t out[4]);
 int mcgpu_probe_packet_rand(mcgpu_ctx *ctx, uint64_t seed, uint64_t packet,
                             int n, float *out);
+/*
+ * The packet loop's own math on n chosen arguments, one thread per item (mcfost_amd/csrc/mc_math_probe.hip.h lists the
+ * kinds with their rows): in = n_in rows of n doubles, out = n_out rows of n doubles; integers and default reals travel
+ * as doubles.  The context supplies the device and the stream: no model needs to be loaded.  MCGPU_ERR_ARG for an unknown
+ * kind or a row count that is not the kind's.
+ */
+int mcgpu_probe_math(mcgpu_ctx *ctx, int kind, uint64_t n, const double *in, int n_in, double *out, int n_out);
 
 /*
  * The deposit logs' staging and fold on records the caller chooses (mc_binned.hip.h run by whole workgroups; the tests

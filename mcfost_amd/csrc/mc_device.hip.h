@@ -96,7 +96,10 @@ __device__ __forceinline__ double nd_add(double a, double b) {
 // sqrt(x) for x = 0 or x far above the subnormals (x >= 2^-767): the instruction sequence hipcc expands sqrt(double)
 // into -- v_rsq_f64 and two coupled Newton steps -- without the rescaling of tiny arguments and the infinity test
 // that sequence carries for the general case (7 of its 24 vector instructions).  The same bits as sqrt() on that
-// domain; the crossing's discriminants (AU^2) are never anywhere near 1e-231.
+// domain; the crossing's discriminants (AU^2) are never anywhere near 1e-231.  (Held on the device against a correctly
+// rounded root -- random mantissas of either exponent parity over 2^-767 .. 2^80, exact squares and their neighbours,
+// 2e5 arguments next to a rounding midpoint -- and on the host from a 26-bit seed: tests/test_device_math_gpu.py,
+// tests/test_device_math_emulated.py.)
 __device__ __forceinline__ double sqrt_nonneg(double x) { return sqrt_nonneg_from_seed(x, __builtin_amdgcn_rsq(x)); }
 #endif
 // (int)x for x >= 0 that may be far beyond the integers: v_cvt_i32_f64 saturates and gives 0 for a NaN.  The C++ cast is
@@ -123,7 +126,8 @@ __device__ __forceinline__ unsigned int sad_plus1_u32(unsigned int a, unsigned i
 #endif
 }
 // ... without the last correction step: within a few units in the last place (the flight-parametric crossing, which
-// makes no claim on the reference's last bits)
+// makes no claim on the reference's last bits); the tests allow 4 -- measured on the device over the 6.6e5 arguments of
+// tests/device_math_cases.py::sqrt_inputs: 0, every root came out correctly rounded
 __device__ __forceinline__ double sqrt_fast_nonneg(double x) {
 #ifdef MCGPU_LANE_EMULATION
   return sqrt(x);
@@ -141,7 +145,10 @@ __device__ __forceinline__ double sqrt_fast_nonneg(double x) {
 }
 
 // log(x) for positive, finite, normal x: frexp, s = (m - 1) / (m + 1) with m in [sqrt(1/2), sqrt(2)), the series
-// 2 s (1 + s^2 / 3 + ... + s^18 / 19) and e ln 2 -- 4e-16 of libm's log (2 ulp; checked over 5e6 arguments on the host),
+// 2 s (1 + s^2 / 3 + ... + s^18 / 19) and e ln 2 -- within 7e-16 (relative) of the logarithm: measured on the device
+// against an extended-precision log, 4.61e-16 at worst (x = 1.317...; 11 of 1.1e6 arguments beyond the 4e-16 this
+// comment used to state) and 4.23e-16 over all 2^24 optical depths, plus one ulp of margin
+// (tests/test_device_math_gpu.py) --
 // 35 vector instructions against the 98 of the library routine, which carries a double-double tail for its last bit.
 // The packet loop takes two logarithms per interaction: the optical depth of the next flight, -log(1 - rand)
 // (dust_transfer.f90:1208-1215 -- in default real there) and Temp_LTE's log(Qheat) (thermal_emission.f90:684).
@@ -1150,10 +1157,12 @@ __device__ inline void cdapres(double cospsi, double phi, double u0, double v0, 
 }
 // sin and cos of pi * x: what every azimuth of the packet loop is -- phi = pi (2 rand - 1) (utils.f90 / dust_transfer.f90:
 // 1297, random_numbers.f90:44) -- without forming pi * x first: sincospi reduces its argument exactly (71 vector
-// instructions against the 158 of sincos); the same numbers to the rounding of the product pi * x
+// instructions against the 158 of sincos); the same numbers to the rounding of the product pi * x.  The host form takes
+// that product of x in [-1, 1): an azimuth 2 rand in [1, 2) gives up its period first (x - 2 is exact), or the product
+// in [pi, 2 pi) would round twice as coarsely -- 6.9e-16 from sin(pi x) instead of 3.5e-16 (tests/test_device_math_emulated.py)
 __device__ inline void sincos_pi(double x, double* s, double* c) {
 #ifdef MCGPU_LANE_EMULATION
-  sincos(PI * x, s, c);
+  sincos(PI * (x >= 1.0 ? x - 2.0 : x), s, c);
 #else
   sincospi(x, s, c);
 #endif
@@ -1555,6 +1564,25 @@ __device__ inline int select_scattering_grain(const DevModel& M, int cls, int la
   return k;
 }
 
+// hg (scattering.f90:1354-1383): the Henyey-Greenstein draw's cosine of the scattering angle and its angle bin.  The
+// quotient form rounds a hair outside [-1, 1] for some g at the ends of the draw (rand = 0: by up to 2^-54 / |g|), where
+// cdapres' sqrt(1 - cospsi^2) and acos would be NaN: the cosine is clamped (DESIGN.md "One deliberate deviation ...").
+// (hg_cosine: the reference's expression as it stands, before the clamp -- apart from hg_draw only the math probe calls it)
+__device__ __forceinline__ double hg_cosine(float gg, float rand) {
+  const double rand_dp = fmin((double)rand, 1.0 - 1e-6);
+  if (fabsf(gg) > 1.17549435e-38f) {
+    const double g1 = (double)gg, g2 = g1 * g1;
+    const double q = (1.0 - g2) / (1.0 - g1 + 2.0 * g1 * rand_dp);
+    return (1.0 + g2 - q * q) / (2.0 * g1);
+  }
+  return 2.0 * rand_dp - 1.0;
+}
+__device__ __forceinline__ void hg_draw(float gg, float rand, int nang, int& itheta, double& cospsi) {
+  cospsi = fmin(fmax(hg_cosine(gg, rand), -1.0), 1.0);
+  itheta = (int)floor(acos(cospsi) * 180.0 / PI) + 1;
+  if (itheta > nang) itheta = nang;
+}
+
 template <typename EnergyFn>
 __device__ __forceinline__ bool interact_direction(const Lds& T, const DevModel& M, const float g[8], int& lambda,
                                                    double u, double v, double w, double& u1, double& v1, double& w1,
@@ -1605,16 +1633,7 @@ __device__ __forceinline__ bool interact_direction(const Lds& T, const DevModel&
     } else {
       // hg (scattering.f90:1354-1383); method 1: with the grain's asymmetry parameter (dust_transfer.f90:1307)
       const float gg = m1 ? M.m1_g[(size_t)(igrain - 1) + (size_t)M.m1_ng * (lambda - 1)] : T.g[lambda - 1];
-      const double rand_dp = fmin((double)rand, 1.0 - 1e-6);
-      if (fabsf(gg) > 1.17549435e-38f) {
-        const double g1 = (double)gg, g2 = g1 * g1;
-        const double q = (1.0 - g2) / (1.0 - g1 + 2.0 * g1 * rand_dp);
-        cospsi = (1.0 + g2 - q * q) / (2.0 * g1);
-      } else {
-        cospsi = 2.0 * rand_dp - 1.0;
-      }
-      itheta = (int)floor(acos(cospsi) * 180.0 / PI) + 1;
-      if (itheta > M.nang) itheta = M.nang;
+      hg_draw(gg, rand, M.nang, itheta, cospsi);
     }
     if (M.lisotropic && !(m1 && M.aniso_method == 1)) { itheta = 1; cospsi = 2.0 * (double)rand - 1.0; }
     phi = 2.0 * (double)rand_phi - 1.0;

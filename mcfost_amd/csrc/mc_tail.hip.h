@@ -263,17 +263,7 @@ __device__ __forceinline__ bool tail_packet(const Lds& T, const DevModel& M, con
           const double c0 = T.cost[itheta - 1], c1 = T.cost[itheta];
           cospsi = c0 + (double)g2 * (c1 - c0);
         } else {  // hg (scattering.f90:1354-1383)
-          const float gg = T.g[lambda - 1];
-          const double rand_dp = fmin((double)g1, 1.0 - 1e-6);
-          if (fabsf(gg) > 1.17549435e-38f) {
-            const double ga = (double)gg, gb = ga * ga;
-            const double qq = (1.0 - gb) / (1.0 - ga + 2.0 * ga * rand_dp);
-            cospsi = (1.0 + gb - qq * qq) / (2.0 * ga);
-          } else {
-            cospsi = 2.0 * rand_dp - 1.0;
-          }
-          itheta = (int)floor(acos(cospsi) * 180.0 / PI) + 1;
-          if (itheta > M.nang) itheta = M.nang;
+          hg_draw(T.g[lambda - 1], g1, M.nang, itheta, cospsi);
         }
         if (M.lisotropic) { itheta = 1; cospsi = 2.0 * (double)g1 - 1.0; }
         sphi = __shfl(B.ss, q); cphi = __shfl(B.cs, q);

@@ -36,6 +36,7 @@
 #include "mc_xilog.hip.h"
 #include "mc_stage_probe.hip.h"
 #include "mc_commit_probe.hip.h"
+#include "mc_math_probe.hip.h"
 
 using namespace mcgpu;
 
@@ -4234,6 +4235,24 @@ extern "C" int mcgpu_probe_philox(mcgpu_ctx* ctx, const uint32_t ctr[4], const u
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(d.get(out, 4));
+  return MCGPU_OK;
+}
+
+// The packet loop's own math on chosen arguments (mc_math_probe.hip.h): the context gives the device and the stream only.
+extern "C" int mcgpu_probe_math(mcgpu_ctx* ctx, int kind, uint64_t n, const double* in, int n_in, double* out, int n_out) {
+  if (!ctx) return MCGPU_ERR_ARG;
+  int want_in = 0, want_out = 0;
+  if (!math_probe_rows(kind, want_in, want_out)) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_math: unknown kind");
+  if (n_in != want_in || n_out != want_out) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_math: wrong number of rows for this kind");
+  if (n < 1 || n > (1ull << 28) || !in || !out) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_probe_math: bad argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  DevArr<double> d_in, d_out;
+  HIPCHK(d_in.resize((size_t)n * n_in)); HIPCHK(d_in.put(in, (size_t)n * n_in));
+  HIPCHK(d_out.resize((size_t)n * n_out));
+  hipLaunchKernelGGL(k_probe_math, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, ctx->stream, kind, (size_t)n, d_in.p, d_out.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(d_out.get(out, (size_t)n * n_out));
   return MCGPU_OK;
 }
 

@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "mcgpu_repartition_energie", "mcgpu_opacity", "mcgpu_set_variable_dust_s11", "mcgpu_set_scattering_method1", "mcgpu_set_rt2", "mcgpu_fetch_I_spec", "mcgpu_rt1_stars_map_image", "mcgpu_set_I_spec", "mcgpu_rt2_source", "mcgpu_rt2_dust_map", "mcgpu_rt2_image", "mcgpu_shard_packets", "mcgpu_multi_run_thermal", "mcgpu_multi_run_mono", "mcgpu_multi_run_sed", "mcgpu_multi_rccl_ranks", "mcgpu_multi_create_ex", "mcgpu_multi_reductions", "mcgpu_set_mrw_exit_spectrum", "mcgpu_voronoi_tesselation", "mcgpu_build_ksca_CDF", "mcgpu_init_reemission_ex", "mcgpu_tau_maps",
     "mcgpu_set_nlte", "mcgpu_init_reemission_nlte", "mcgpu_set_J0", "mcgpu_temp_finale_nlte", "mcgpu_set_Tdust_1grain",
     "mcgpu_probe_reemission_nlte", "mcgpu_probe_bin_stage", "mcgpu_probe_xi_sort_fold", "mcgpu_probe_xi_commit",
+    "mcgpu_probe_math",
 )
 
 
@@ -187,6 +188,23 @@ class Engine:
             self.device = device
             self._upload(model, float(n_packets_total))
             return
+        self._create(device)
+        self._upload(model, float(n_packets_total))
+
+    @classmethod
+    def bare(cls, device: int = 0):
+        """A context without a model -- the device and its stream -- for the probes that need no tables
+        (``probe_math``, ``probe_philox``, ``probe_packet_rand``)."""
+        self = cls.__new__(cls)
+        self.lib = load_library()
+        self.model = None
+        self.nlte = None
+        self.ctx = C.c_void_p()
+        self._owns_ctx = True
+        self._create(device)
+        return self
+
+    def _create(self, device):
         # If this process also uses torch (device_accumulators / device_xI hand the engine's buffers to it), torch
         # must initialise its HIP context first: torch wheels carry their own HIP runtime, and brought up second it
         # has been seen to report "No HIP GPUs are available".
@@ -204,7 +222,6 @@ class Engine:
             raise McgpuError(f"mcgpu_create(device={device}) failed with code {rc} "
                              "(1 = no usable HIP device; the engine has no CPU path)")
         self.device = device
-        self._upload(model, float(n_packets_total))
 
     # -- plumbing ----------------------------------------------------------
     def _chk(self, rc, what):
@@ -944,6 +961,25 @@ class Engine:
         o = (C.c_uint32 * 4)()
         self._chk(self.lib.mcgpu_probe_philox(self.ctx, c, k, o), "mcgpu_probe_philox")
         return [int(v) for v in o]
+
+    # the kinds of mcgpu_probe_math (mcfost_amd/csrc/mc_math_probe.hip.h::MathProbeKind) with their rows (in, out)
+    MATH_KINDS = {"sqrt_nonneg": (0, 1, 1), "sqrt_fast_nonneg": (1, 1, 1), "log_pos": (2, 1, 1), "tau_of_draw": (3, 1, 1),
+                  "f64_to_i32_sat": (4, 1, 1), "sad_plus1_u32": (5, 2, 1), "sincos_pi": (6, 1, 2),
+                  "az_sector_certain": (7, 3, 2), "az_sector": (8, 3, 2), "cdapres_pi": (9, 5, 3), "rotation": (10, 6, 3),
+                  "stokes_rotation": (11, 6, 2), "stokes_apply": (12, 12, 4), "hg": (13, 3, 3)}
+
+    def probe_math(self, kind, *rows):
+        """The packet loop's own math on chosen arguments (``mcgpu_probe_math``): ``rows`` are the kind's input rows
+        (scalars are broadcast); returns its output rows, float64 ``[n_out, n]``."""
+        code, n_in, n_out = self.MATH_KINDS[kind]
+        assert len(rows) == n_in, (kind, len(rows), n_in)
+        ins = np.ascontiguousarray(np.broadcast_arrays(*[np.asarray(r, np.float64) for r in rows]), dtype=np.float64)
+        ins = ins.reshape(n_in, -1)
+        n = ins.shape[1]
+        out = np.empty((n_out, n), np.float64)
+        self._chk(self.lib.mcgpu_probe_math(self.ctx, C.c_int(code), C.c_uint64(n), _p(ins, C.c_double), C.c_int(n_in),
+                                            _p(out, C.c_double), C.c_int(n_out)), "mcgpu_probe_math")
+        return out
 
     def probe_bin_stage(self, kind, keys, vals, out, grid_blocks, block_threads, n_buckets, shift, total_blocks, n_out,
                         n_launches=1, fold_threads=1024, split=1, slice_sub=None, nRT=1, contrib=False):

@@ -1146,6 +1146,8 @@ void oracle_hg(float g, float rand, int nang_scatt, int *itheta,
   } else {
     *cospsi = 2.0 * rand_dp - 1.0;
   }
+  /* the quotient form rounds outside [-1, 1] at the ends of the draw for some g: clamped, like hg_draw */
+  *cospsi = fmin(fmax(*cospsi, -1.0), 1.0);
   *itheta = (int)floor(acos(*cospsi) * 180.0 / PI) + 1;
   if (*itheta > nang_scatt) *itheta = nang_scatt;
 }
