@@ -247,6 +247,19 @@ int mcgpu_set_midplane_snap(mcgpu_ctx *ctx, int on);
  *                      any (mcgpu_get_info "nlte_events", "nlte_visits"; a diagnostic, off by default)
  *   "radiation_field"  bit 0: keep xN_abs, bit 1: keep xJ_abs in the thermal step (mcgpu_fetch_radiation_field);
  *                      cylindrical grids then run the single-role kernel
+ *   "radiation_field_sed"  SED mode (mcgpu_run_mono): bit 0: keep xJ_abs, bit 1: keep xN_abs (lProDiMo) of the SED step, per
+ *                      cell and wavelength (mcgpu_fetch_radiation_field_sed, mcgpu_compute_J, mcgpu_compute_UV_field).
+ *                      Default 0: every launch is what it is without the option.  While it is on, the commit passes run
+ *                      kernels of their own that know the extra deposit and add xI_scatt with atomics: "xi_log" = 1, 2
+ *                      and 3 then run as 0 (the kernels that log their deposits do not keep the field); the automatic
+ *                      choice of "xi_log" is otherwise untouched.  mcgpu_multi_run_mono and mcgpu_multi_run_sed refuse.
+ *   "xj_where"     a tuning knob of "radiation_field_sed": where a crossing adds to xJ_abs.  0 (default) = automatic: on 2D
+ *                      cylindrical / spherical grids with one dust class the wavelength's row (n_cells doubles) is kept in
+ *                      the workgroup's LDS and folded into HBM once per workgroup, where that does not cost the
+ *                      workgroup its place on the CU; else one FP64 atomic to HBM per crossing.  1 = HBM atomics always;
+ *                      2 = the LDS row wherever it fits at all, and MCGPU_ERR_UNSUPPORTED from mcgpu_run_mono where
+ *                      it does not (3D and Voronoi grids, dust classes, rows beyond the LDS).  The same sums to the
+ *                      order of the additions.  mcgpu_get_info "xj_lds": what the last commit launch did.
  * Results do not depend on any of them (same packets, same random numbers) -- except "crossing" = 1, which changes
  * the crossing's arithmetic (statistical parity only), and to the rounding of a sum's order ("tail_where": a host
  * thread evaluates log / sin / cos with the host's libm, the device with its own: a packet's history is the same
@@ -901,6 +914,42 @@ int mcgpu_build_ksca_CDF(mcgpu_ctx *ctx, int build, double *ksca_CDF_out);
  * launches fetch and reset it in between.
  */
 int mcgpu_fetch_radiation_field(mcgpu_ctx *ctx, double *xN_abs, double *xJ_abs);
+
+/*
+ * The mean radiation field of the SED step: save_radiation_field's step-2 branch (radiation_field.f90:57-61).  With
+ * mcgpu_set_option(ctx, "radiation_field_sed", bits) -- bit 0: xJ_abs, bit 1: xN_abs (lProDiMo) -- every crossing of a
+ * cell that exists (lcell_not_empty; a dark cell mirrors the packet first, the scout pass deposits nothing) by a packet
+ * of mcgpu_run_mono's commit pass adds l * Stokes(1) to xJ_abs(icell, lambda) and 1 to xN_abs(icell, lambda), with or
+ * without ray-tracing deposits (opts->rt1 = 0, 1 or 2).  Switching the option on allocates and zeroes both
+ * [n_lambda][n_cells] arrays; a run of wavelength lambda ADDS to row lambda, whatever opts->accumulate says, as the
+ * reference's step 2 accumulates, and leaves the other rows alone; mcgpu_reset_radiation_field_sed zeroes both arrays;
+ * a new grid drops them (the next mcgpu_run_mono allocates them again, zeroed).
+ * mcgpu_fetch_radiation_field_sed returns them column-major (icell, lambda) like mcgpu_fetch_radiation_field; either
+ * pointer may be NULL; MCGPU_ERR_STATE where the array asked for was not kept.
+ * xN_abs is counted in 32-bit words on the device: a cell crossed more than 2^32 times at one wavelength between two
+ * resets wraps (the reference's default-real counter stops growing at 2^24 instead).
+ * One context only: no reduction or gather of the rows across contexts is built, and mcgpu_multi_run_mono /
+ * mcgpu_multi_run_sed return MCGPU_ERR_UNSUPPORTED while the option is on in one of their contexts.
+ */
+int mcgpu_reset_radiation_field_sed(mcgpu_ctx *ctx);
+int mcgpu_fetch_radiation_field_sed(mcgpu_ctx *ctx, double *xJ_abs, double *xN_abs);
+/*
+ * ecriture_J's step-2 branch (output.f90:2280-2286) on the device, from the xJ_abs kept above:
+ *   photon_energy(lambda) = hp c^2 / 2 (E_stars + E_disk) / n_sent * tab_lambda * 1e-6
+ *   Jio(icell, lambda) = (xJ_abs + J0) * photon_energy / volume(icell)        default real, W m^-2 (lambda F_lambda)
+ * n_sent, E_stars, E_disk, tab_lambda (micron): [n_lambda]; J0: (icell, lambda) column-major like Jio, or NULL (zeros:
+ * the ISM packet loop of the ProDiMo / ML couplings, dust_transfer.f90:942-989, is the host's).  A wavelength with
+ * n_sent = 0 makes the reference divide by zero: MCGPU_ERR_ARG, and mcgpu_last_error names the wavelength.
+ */
+int mcgpu_compute_J(mcgpu_ctx *ctx, const double *n_sent, const double *E_stars, const double *E_disk,
+                    const double *tab_lambda, const double *J0, float *Jio);
+/*
+ * compute_UV_field (output.f90:2458-2519), one thread per cell: J in F_lambda (no tab_lambda * 1e-6 factor) interpolated
+ * (interp without extrapolation, utils.f90:190 ff.) at the 200 wavelengths span(0.0912, 0.2, 200) * 1e-6 -- the
+ * reference's default-real running sum -- and integrated by the trapezoid, in Habing: G[n_cells], default real.
+ */
+int mcgpu_compute_UV_field(mcgpu_ctx *ctx, const double *n_sent, const double *E_stars, const double *E_disk,
+                           const double *tab_lambda, const double *J0, float *G);
 
 /*
  * Grains in radiative equilibrium but out of LTE (lRE_nLTE, methode_chauffage = 2, read_param.f90:322-324): one

@@ -40,6 +40,10 @@ const void* kpick_mono(bool l3d, bool pola, bool dark, bool scout, bool f32, boo
 const void* kpick_mono_rec(bool l3d, bool dark);
 const void* kpick_mono_sph(bool l3d, bool pola, bool scout, bool f32);
 const void* kpick_mono_voro(bool pola, bool scout, bool f32);
+// kern_mono_xj.hip: the commit pass that also keeps xJ_abs / xN_abs of the SED step -- k_mono_xj, k_mono_sph_xj, k_mono_voro_xj
+const void* kpick_mono_xj(bool l3d, bool pola, bool dark, bool f32);
+const void* kpick_mono_sph_xj(bool l3d, bool pola, bool f32);
+const void* kpick_mono_voro_xj(bool pola, bool f32);
 
 // kern_nlte.hip: the grains out of LTE (mc_nlte.hip.h) -- k_thermal_nlte (cylindrical grids, one dust class, no random
 // walk), k_probe_reemission_nlte, k_temp_finale_nlte, k_init_reemission_nlte, k_repart_nlte

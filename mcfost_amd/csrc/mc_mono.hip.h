@@ -77,6 +77,11 @@ struct MonoArgs {
   int rowf;                             // COMMIT: > 0: the per-lane results are weight rows of this many default reals
   // the commit pass's deposits as 16-byte records in a binned log (k_mono_rec; mc_xirec.hip.h)
   XiRecLog rec;
+  // the mean radiation field of the SED step (option "radiation_field_sed"; the k_mono*_xj kernels, "The mean radiation
+  // field" below): this wavelength's rows of xJ_abs / xN_abs, (1:n_cells) each, or null
+  double* xJ;
+  unsigned int* xN;
+  int xj_lds;                           // the workgroup keeps a private copy of xJ's row in its LDS and folds it at the end
 };
 
 // per-lane results of angles_scatt_rt1, kept in LDS as [q][thread]
@@ -99,8 +104,9 @@ struct RtScratch {
 // rowf > 0 (the commit pass with default-real records and one dust class on cylindrical / spherical grids): the per-lane
 // results are the flight's deposit weights as a row of rowf default reals in the sub-bin's order (xi32_row_floats) instead
 // of (cosw, sinw, itheta), and the tiles carry no slot masks.
+// xj_cells > 0 (the k_mono*_xj kernels, MonoArgs::xj_lds): the workgroup's private row of xJ_abs behind everything else.
 __host__ __device__ inline size_t mono_lds_bytes(const DevModel& M, int nRT, int threads, bool pola, bool slim, bool log = false,
-                                                 int kf_cells = 0, int rowf = 0) {
+                                                 int kf_cells = 0, int rowf = 0, int xj_cells = 0) {
   size_t b = (lds_bytes(M, slim) + 7) / 8 * 8;
   b += (size_t)6 * (M.nang + 1) * sizeof(float);                     // the Mueller columns of p_lambda
   b = (b + 7) / 8 * 8;
@@ -118,6 +124,7 @@ __host__ __device__ inline size_t mono_lds_bytes(const DevModel& M, int nRT, int
   b = (b + 7) / 8 * 8;
   b += (size_t)3 * nRT * sizeof(double);                             // the observers' rotation constants
   b += (size_t)kf_cells * sizeof(double);                            // kappa_factor
+  b += (size_t)xj_cells * sizeof(double);                            // the private row of xJ_abs
   return b;
 }
 
@@ -999,13 +1006,59 @@ __device__ inline void xlog_append(const MonoArgs& A, XiLogCursor& C, bool on, u
 }
 #endif
 
+// ---- The mean radiation field of the SED step -------------------------------------------------------------------------
+// save_radiation_field's step-2 branch (radiation_field.f90:57-61): every crossing of a cell that exists adds
+// l * Stokes(1) to xJ_abs(icell, lambda) and, with ProDiMo, 1 to xN_abs(icell, lambda).  Kernels of their own
+// (k_mono_xj, k_mono_sph_xj, k_mono_voro_xj: mono_body's XJ) so that the commit kernels of a context without the
+// option are what they were.  Where: HBM, one native FP64 atomic per crossing issued with the crossing's other atomics
+// -- fire and forget like them, no load is gained that would wait for it (see mono_lds_bytes on vmcnt) --, or, on 2D
+// grids with one dust class whose row fits (launch_mono decides as for kf_lds), a private row in the workgroup's LDS:
+// zeroed at entry, ds_add_f64 per crossing, folded into the HBM row with FP64 atomics once, behind a barrier that every
+// wave reaches after its own packet loop has ended.  xN_abs: 32-bit counts in HBM (ProDiMo only).
+__device__ __forceinline__ void mono_xj_deposit(const MonoArgs& A, double* xj_row_lds, int ic, double l_S0) {
+#ifndef MCGPU_LANE_EMULATION
+  if (xj_row_lds) {
+    typedef __attribute__((address_space(3))) double lds_f64_t;
+    __hip_atomic_fetch_add((lds_f64_t*)xj_row_lds + ic, l_S0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_add_f64
+  } else
+#endif
+  if (A.xJ) unsafeAtomicAdd(&A.xJ[ic], l_S0);
+  if (A.xN) atomicAdd(&A.xN[ic], 1u);
+}
+
+// the workgroup's private row: behind kappa_factor (mono_lds_setup; mono_lds_bytes' xj_cells), zeroed
+__device__ __forceinline__ double* mono_xj_row_setup(const DevModel& M, const MonoArgs& A, const double* rot) {
+  if (!A.xj_lds) return nullptr;
+  double* row = const_cast<double*>(rot) + (size_t)3 * A.nRT + (A.kf_lds ? (size_t)M.n_cells : 0);
+  for (int i = threadIdx.x; i < M.n_cells; i += blockDim.x) row[i] = 0.0;
+  __syncthreads();
+  return row;
+}
+
+// ... and its fold, by the whole workgroup (the workgroups start at different cells: they finish at about the same
+// time, and the same addresses' atomics serialise at the memory side)
+__device__ __forceinline__ void mono_xj_row_fold(const DevModel& M, const MonoArgs& A, const double* row) {
+  if (!row) return;   // (workgroup-uniform)
+  __syncthreads();
+  const int n = M.n_cells;
+  const int off = (int)(((unsigned long long)blockIdx.x * blockDim.x) % (unsigned long long)n);
+  for (int j = threadIdx.x; j < n; j += blockDim.x) {
+    int i = j + off;
+    if (i >= n) i -= n;
+    const double v = row[i];
+    if (v != 0.0) unsafeAtomicAdd(&A.xJ[i], v);
+  }
+}
+
 // SCOUT: no deposits, no SED; records hits.  Otherwise the COMMIT pass.
 // SPH: the grid operators of spherical_grid.f90 (as thermal_body has them)
 // LOG (with F32, one dust class): the deposits go to the log instead of xI_scatt (see "The deposits as a log")
 // REC (with F32, one dust class, no Stokes tracking, <= 3 observers): a deposit is a 16-byte record {sub-bin, l * w[q]}
 // handed to the staging of mc_binned.hip.h (mc_xirec.hip.h); the lane keeps its flight's weights itself, so the kernel
 // has LOG's LDS -- no per-lane results, no tiles -- plus the staging buckets behind it
-template <bool L3D, bool POLA, bool DARK, bool SCOUT, bool F32 = false, bool SPH = false, bool LOG = false, bool REC = false>
+// XJ (a commit pass with atomic deposits): xJ_abs / xN_abs of the SED step ("The mean radiation field" above)
+template <bool L3D, bool POLA, bool DARK, bool SCOUT, bool F32 = false, bool SPH = false, bool LOG = false, bool REC = false,
+          bool XJ = false>
 __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, double* lds_base) {
   const Lds T = lds_carve(lds_base, M, true);
   lds_stage_mono(T, M, A.p_lambda);
@@ -1016,7 +1069,8 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
   double* const tile = ML.tile;
   unsigned long long* const tile_addr = ML.tile_addr;
   unsigned int* const tile_mask = ML.tile_mask;
-
+  double* xj_row = nullptr;
+  if constexpr (XJ) xj_row = mono_xj_row_setup(M, A, R.rot);
 
   const int lane = threadIdx.x & 63;
   const int n_rad = M.n_rad, nz = M.nz;
@@ -1200,6 +1254,8 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
       }
       RtDeposit dep;
       dep.on = false; dep.icell = 1; dep.phik = 1; dep.psup = 1; dep.l = 0.0;
+      int xj_ic = -1;        // XJ: the cell and the path of this crossing's deposit into xJ_abs
+      double xj_l = 0.0;
       if (st == S_FLIGHT) {
         const int azj = zj < 0 ? -zj : zj;
         const bool out = (ri == n_rad + 1) || (!SPH && (azj == nz + 1) && (fabs(z) > M.zmaxmax));   // (test_exit_grid_sph: the outer radius only)
@@ -1241,6 +1297,7 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
             const double tau = l * opacity;
             if (tau > extr) {
               const double lc = l * (extr / tau);
+              if constexpr (XJ) { if (real_cell) { xj_ic = ic; xj_l = lc; } }
               if (!SCOUT && A.rt1 && real_cell) {
                 dep.on = true; dep.icell = ic + 1; dep.l = lc;
                 rt1_subbin<L3D>(A, x, y, z, x1, y1, z1, dep.phik, dep.psup);
@@ -1256,6 +1313,7 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
               st = S_INTERACT;
             } else {
               extr = extr - tau;
+              if constexpr (XJ) { if (real_cell) { xj_ic = ic; xj_l = l; } }
               if (!SCOUT && A.rt1 && real_cell) {
                 dep.on = true; dep.icell = ic + 1; dep.l = l;
                 rt1_subbin<L3D>(A, x, y, z, x1, y1, z1, dep.phik, dep.psup);
@@ -1303,6 +1361,7 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
 #endif
         deposit_rt1_wave<POLA>(M, A, R, mu, dep, S, flag_star, tile, tile_addr, tile_mask);
       }
+      if constexpr (XJ) { if (xj_ic >= 0) mono_xj_deposit(A, xj_row, xj_ic, xj_l * S[0]); }
     }
 #ifndef MCGPU_LANE_EMULATION
     if (REC) bin_settle(RS, A.rec, RK, lane, RP);   // (wave-uniform: the flushes this wave owes, before it turns to emission and interactions)
@@ -1319,6 +1378,7 @@ __device__ __forceinline__ void mono_body(const DevModel& M, const MonoArgs& A, 
     if (lane == 0 && n_rec) atomicAdd(&A.rec.stats[3], n_rec);
   }
 #endif
+  if constexpr (XJ) mono_xj_row_fold(M, A, xj_row);
 
   if (!SCOUT) {
     unsigned int cs[8] = {c_pack, c_cross, c_flight, c_scatt, c_abs, c_esc, c_kill, c_dark};
@@ -1355,6 +1415,19 @@ template <bool L3D, bool POLA, bool SCOUT, bool F32 = false>
 __global__ void __launch_bounds__(512) k_mono_sph(const DevModel M, const MonoArgs A) {
   extern __shared__ double lds_raw[];
   mono_body<L3D, POLA, false, SCOUT, F32, true>(M, A, lds_raw);
+}
+
+// The commit pass that also keeps xJ_abs / xN_abs of the SED step (mono_body's XJ).  Kernels of their own names: the
+// instantiations above keep their symbols and their code.
+template <bool L3D, bool POLA, bool DARK, bool F32>
+__global__ void __launch_bounds__(512) k_mono_xj(const DevModel M, const MonoArgs A) {
+  extern __shared__ double lds_raw[];
+  mono_body<L3D, POLA, DARK, false, F32, false, false, false, true>(M, A, lds_raw);
+}
+template <bool L3D, bool POLA, bool F32>
+__global__ void __launch_bounds__(512) k_mono_sph_xj(const DevModel M, const MonoArgs A) {
+  extern __shared__ double lds_raw[];
+  mono_body<L3D, POLA, false, false, F32, true, false, false, true>(M, A, lds_raw);
 }
 
 // Stopping index of every active stream from this batch's hit flags: one wave per stream.

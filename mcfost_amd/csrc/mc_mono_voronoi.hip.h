@@ -8,7 +8,8 @@
 
 namespace mcgpu {
 
-template <bool POLA, bool SCOUT, bool F32 = false>
+// XJ (a commit pass): xJ_abs / xN_abs of the SED step, one HBM atomic per crossing (mc_mono.hip.h "The mean radiation field")
+template <bool POLA, bool SCOUT, bool F32 = false, bool XJ = false>
 __device__ __forceinline__ void mono_body_voro(const DevModel& M, const MonoArgs& A, const VoroGrid& G,
                                                double* lds_base) {
   const Lds T = lds_carve(lds_base, M, true);
@@ -131,6 +132,8 @@ __device__ __forceinline__ void mono_body_voro(const DevModel& M, const MonoArgs
       }
       RtDeposit dep;
       dep.on = false; dep.icell = 1; dep.phik = 1; dep.psup = 1; dep.l = 0.0;
+      int xj_ic = -1;
+      double xj_l = 0.0;
       if (st == S_FLIGHT) {
         if (icell < 0) {
           st = S_EXITED;
@@ -148,6 +151,7 @@ __device__ __forceinline__ void mono_body_voro(const DevModel& M, const MonoArgs
           const bool stop = tau > extr;
           const double lc = stop ? l_contrib * (extr / tau) : l_contrib;
           if (!SCOUT && A.rt1) { dep.on = true; dep.icell = icell; dep.l = lc; }  // save_radiation_field(l_contrib)
+          if constexpr (XJ) { xj_ic = icell - 1; xj_l = lc; }
           if (stop) {
             const double ls = l_void + lc;
             x = nd_add(x, nd_mul(ls, u));
@@ -174,6 +178,7 @@ __device__ __forceinline__ void mono_body_voro(const DevModel& M, const MonoArgs
 #endif
         deposit_rt1_wave<POLA>(M, A, ML.R, ML.mu, dep, S, flag_star, ML.tile, ML.tile_addr, ML.tile_mask);
       }
+      if constexpr (XJ) { if (xj_ic >= 0) mono_xj_deposit(A, nullptr, xj_ic, xj_l * S[0]); }
     }
   }
 
@@ -195,6 +200,12 @@ template <bool POLA, bool SCOUT, bool F32 = false>
 __global__ void __launch_bounds__(512) k_mono_voro(const DevModel M, const MonoArgs A, const VoroGrid G) {
   extern __shared__ double lds_raw[];
   mono_body_voro<POLA, SCOUT, F32>(M, A, G, lds_raw);
+}
+
+template <bool POLA, bool F32>
+__global__ void __launch_bounds__(512) k_mono_voro_xj(const DevModel M, const MonoArgs A, const VoroGrid G) {
+  extern __shared__ double lds_raw[];
+  mono_body_voro<POLA, false, F32, true>(M, A, G, lds_raw);
 }
 
 }  // namespace mcgpu

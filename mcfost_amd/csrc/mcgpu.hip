@@ -205,6 +205,14 @@ struct mcgpu_ctx {
   int opt_radiation_field = 0;   // bit 0: xN_abs, bit 1: xJ_abs (thermal step; radiation_field.f90:54-55)
   DevArr<unsigned long long> d_xN;   // [n_cells] (64-bit: a hot cell passes 2^32 segments within one 1e9-packet run)
   DevArr<double> d_xJ;           // (n_cells, n_lambda)
+  // the SED step's own (save_radiation_field's step-2 branch, radiation_field.f90:57-61; the k_mono*_xj kernels)
+  int opt_radiation_field_sed = 0;   // bit 0: xJ_abs, bit 1: xN_abs (lProDiMo)
+  int opt_xj_where = 0;              // 0 = automatic, 1 = HBM atomics, 2 = the workgroup's private row in LDS
+  DevArr<double> d_xJ_sed;           // (n_cells, n_lambda)
+  DevArr<unsigned int> d_xN_sed;     // (n_cells, n_lambda), 32-bit counts
+  DevArr<double> d_xJ_keep;          // [n_cells] a wavelength's row of xJ_abs as mcgpu_run_mono found it ...
+  DevArr<unsigned int> d_xN_keep;    // ... and of xN_abs: what a speculative commit that overshot puts back
+  int last_xj_lds = 0;               // the last commit launch kept its row of xJ_abs in LDS (mcgpu_get_info "xj_lds")
   std::vector<DevArr<char>> allocs;   // every table buffer (upload(); freed with the context)
   // views of tables in `allocs` that a later setter patches
   int *d_cmi = nullptr, *d_cmj = nullptr, *d_cmk = nullptr;
@@ -596,6 +604,7 @@ static void grid_release(mcgpu_ctx* ctx) {
   ctx->prob_E_lambda = 0;
   ctx->d_xN.reset();
   ctx->d_xJ.reset();
+  ctx->d_xJ_sed.reset(); ctx->d_xN_sed.reset(); ctx->d_xJ_keep.reset(); ctx->d_xN_keep.reset();
   ctx->d_E_prior.reset();
   nlte_release(ctx, true);   // (the non-LTE tables, J0 and xJ_abs are per cell)
 }
@@ -622,6 +631,26 @@ static void xi_rec_release(mcgpu_ctx* ctx) {
   ctx->xrec_total_blocks = 0;
   ctx->xrec_max_parts = 0;
   ctx->xrec_log_capped = false;
+}
+
+// xJ_abs / xN_abs of the SED step, [n_lambda][n_cells]: allocated and zeroed when the option asks for them and the grid and
+// the wavelengths are known; a new grid drops them (grid_release)
+static int xj_sed_ensure(mcgpu_ctx* ctx) {
+  const DevModel& M = ctx->M;
+  if (!ctx->have_grid || M.n_cells < 1 || M.n_lambda < 1) return MCGPU_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t n = (size_t)M.n_cells * (size_t)M.n_lambda;
+  if ((ctx->opt_radiation_field_sed & 1) && ctx->d_xJ_sed.n != n) {
+    ctx->d_xJ_sed.reset();
+    HIPCHK(ctx->d_xJ_sed.resize(n));
+    HIPCHK(hipMemsetAsync(ctx->d_xJ_sed, 0, n * sizeof(double), ctx->stream));
+  }
+  if ((ctx->opt_radiation_field_sed & 2) && ctx->d_xN_sed.n != n) {
+    ctx->d_xN_sed.reset();
+    HIPCHK(ctx->d_xN_sed.resize(n));
+    HIPCHK(hipMemsetAsync(ctx->d_xN_sed, 0, n * sizeof(unsigned int), ctx->stream));
+  }
+  return MCGPU_OK;
 }
 
 extern "C" int mcgpu_set_option(mcgpu_ctx* ctx, const char* name, int value) {
@@ -657,6 +686,12 @@ extern "C" int mcgpu_set_option(mcgpu_ctx* ctx, const char* name, int value) {
   else if (!strcmp(name, "voronoi_cache_log_slots")) { if (value < 6 || value > 13) return fail(ctx, MCGPU_ERR_ARG, "voronoi_cache_log_slots: 6..13"); ctx->opt_cache_log_slots = value; }
   else if (!strcmp(name, "nlte_stats")) ctx->opt_nlte_stats = value ? 1 : 0;
   else if (!strcmp(name, "radiation_field")) { if (value < 0 || value > 3) return fail(ctx, MCGPU_ERR_ARG, "radiation_field: bit 0 xN_abs, bit 1 xJ_abs"); ctx->opt_radiation_field = value; }
+  else if (!strcmp(name, "radiation_field_sed")) {
+    if (value < 0 || value > 3) return fail(ctx, MCGPU_ERR_ARG, "radiation_field_sed: bit 0 xJ_abs, bit 1 xN_abs of the SED step");
+    ctx->opt_radiation_field_sed = value;
+    if (value) { int rc = xj_sed_ensure(ctx); if (rc) return rc; }   // (without a grid yet: the first mcgpu_run_mono allocates)
+  }
+  else if (!strcmp(name, "xj_where")) { if (value < 0 || value > 2) return fail(ctx, MCGPU_ERR_ARG, "xj_where: 0 (automatic), 1 (HBM atomics), 2 (LDS)"); ctx->opt_xj_where = value; }
   else return fail(ctx, MCGPU_ERR_ARG, "mcgpu_set_option: unknown option");
   return MCGPU_OK;
 }
@@ -725,6 +760,7 @@ extern "C" int mcgpu_get_info(mcgpu_ctx* ctx, const char* name, double* value) {
       else return fail(ctx, MCGPU_ERR_ARG, "mcgpu_get_info: unknown name");
     }
   }
+  else if (!strcmp(name, "xj_lds")) *value = ctx->last_xj_lds;            // the last commit launch: 1 = its row of xJ_abs was in LDS
   else if (!strcmp(name, "xi_log_chunks")) *value = ctx->xlog_chunks;     // the last mcgpu_run_mono: launches of its commit passes,
   else if (!strcmp(name, "xi_log_records")) *value = (double)ctx->xlog_records;   // records (crossings with a deposit) and
   else if (!strcmp(name, "xi_log_flights")) *value = (double)ctx->xlog_flights;   // flights they logged (0: atomics)
@@ -2349,6 +2385,173 @@ extern "C" int mcgpu_fetch_radiation_field(mcgpu_ctx* ctx, double* xN_abs, doubl
   return MCGPU_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// xJ_abs / xN_abs of the SED step (option "radiation_field_sed"; mc_mono.hip.h "The mean radiation field") and what the
+// reference writes from them: ecriture_J(2) (output.f90:2280-2286), compute_UV_field (output.f90:2458-2519)
+// ---------------------------------------------------------------------------------------------
+extern "C" int mcgpu_reset_radiation_field_sed(mcgpu_ctx* ctx) {
+  int rc = ready(ctx);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (ctx->d_xJ_sed) HIPCHK(hipMemsetAsync(ctx->d_xJ_sed, 0, ctx->d_xJ_sed.n * sizeof(double), ctx->stream));
+  if (ctx->d_xN_sed) HIPCHK(hipMemsetAsync(ctx->d_xN_sed, 0, ctx->d_xN_sed.n * sizeof(unsigned int), ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_fetch_radiation_field_sed(mcgpu_ctx* ctx, double* xJ_abs, double* xN_abs) {
+  int rc = ready(ctx);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const DevModel& M = ctx->M;
+  const size_t n = (size_t)M.n_cells * (size_t)M.n_lambda;
+  if (xJ_abs) {
+    if (!ctx->d_xJ_sed || ctx->d_xJ_sed.n != n) return fail(ctx, MCGPU_ERR_STATE, "xJ_abs of the SED step was not accumulated (option radiation_field_sed bit 0)");
+    HIPCHK(hipMemcpy(xJ_abs, ctx->d_xJ_sed, n * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  if (xN_abs) {
+    if (!ctx->d_xN_sed || ctx->d_xN_sed.n != n) return fail(ctx, MCGPU_ERR_STATE, "xN_abs of the SED step was not accumulated (option radiation_field_sed bit 1)");
+    std::vector<unsigned int> h(n);
+    HIPCHK(hipMemcpy(h.data(), ctx->d_xN_sed, n * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) xN_abs[i] = (double)h[i];
+  }
+  return MCGPU_OK;
+}
+
+// Jio(icell, lambda) = (xJ_abs + J0) * photon_energy(lambda) / volume(icell), default real.  One thread per element.
+static __global__ void k_compute_J(const double* xJ, const double* J0, const double* pe, const double* volume, int n_cells,
+                                   size_t n, float* Jio) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t l = i / (size_t)n_cells, ic = i - l * (size_t)n_cells;
+  Jio[i] = (float)((xJ[i] + (J0 ? J0[i] : 0.0)) * pe[l] / volume[ic]);
+}
+
+// compute_UV_field: one thread per cell.  pe: photon_energy in F_lambda; lamb: tab_lambda * 1e-6 (m); wl: the 200
+// wavelengths of the band (m); interp (utils.f90:190 ff.) without extrapolation, then the trapezoid in Habing.
+constexpr int UV_N = 200;
+static __global__ void k_compute_UV(const double* xJ, const double* J0, const double* pe, const double* lamb, const double* wl,
+                                    const double* volume, int n_cells, int n_lambda, double delta_wl, float* G) {
+  const int ic = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ic >= n_cells) return;
+  const double vol = volume[ic];
+  auto J = [&](int l) {   // (1-based wavelength)
+    const size_t at = (size_t)ic + (size_t)n_cells * (size_t)(l - 1);
+    return (xJ[at] + (J0 ? J0[at] : 0.0)) * pe[l - 1] / vol;
+  };
+  const int n = n_lambda;
+  const bool inc = lamb[n - 1] > lamb[0];
+  double xmin = lamb[0], xmax = lamb[0];
+  for (int l = 1; l < n; ++l) { xmin = fmin(xmin, lamb[l]); xmax = fmax(xmax, lamb[l]); }
+  double sum = 0.0, first = 0.0, last = 0.0;
+  for (int q = 0; q < UV_N; ++q) {
+    const double xp = wl[q];
+    double v;
+    if (xp < xmin) v = inc ? J(1) : J(n);
+    else if (xp > xmax) v = inc ? J(n) : J(1);
+    else if (inc) {
+      int j = 2;
+      for (; j <= n - 1; ++j) if (lamb[j - 1] > xp) break;
+      const double frac = (xp - lamb[j - 2]) / (lamb[j - 1] - lamb[j - 2]);
+      v = J(j - 1) * (1.0 - frac) + J(j) * frac;
+    } else {
+      int j = 2;
+      for (; j <= n - 1; ++j) if (lamb[j - 1] < xp) break;
+      const double frac = (xp - lamb[j - 1]) / (lamb[j - 2] - lamb[j - 1]);
+      v = J(j) * (1.0 - frac) + J(j - 1) * frac;
+    }
+    sum += v;
+    if (q == 0) first = v;
+    if (q == UV_N - 1) last = v;
+  }
+  G[ic] = (float)((sum - 0.5 * (first + last)) * delta_wl / (double)2.67e-6f);
+}
+
+// photon_energy(lambda) = hp c^2 / 2 (E_stars + E_disk) / n_sent [* tab_lambda * 1e-6] on the host, the inputs on the device
+static int xj_outputs_prepare(mcgpu_ctx* ctx, const char* who, const double* n_sent, const double* E_stars, const double* E_disk,
+                              const double* tab_lambda, const double* J0, bool lambda_F_lambda, DevArr<double>& d_pe,
+                              DevArr<double>& d_J0) {
+  const DevModel& M = ctx->M;
+  if (!n_sent || !E_stars || !E_disk || !tab_lambda) return fail(ctx, MCGPU_ERR_ARG, "n_sent, E_stars, E_disk and tab_lambda are needed");
+  const size_t n = (size_t)M.n_cells * (size_t)M.n_lambda;
+  if (!ctx->d_xJ_sed || ctx->d_xJ_sed.n != n) return fail(ctx, MCGPU_ERR_STATE, "xJ_abs of the SED step was not accumulated (option radiation_field_sed bit 0)");
+  std::vector<double> pe(M.n_lambda);
+  for (int l = 0; l < M.n_lambda; ++l) {
+    if (!(n_sent[l] > 0.0)) {   // (the reference divides by zero here)
+      ctx->err = std::string(who) + ": no packets were sent at wavelength " + std::to_string(l + 1) + " (n_sent = 0)";
+      return MCGPU_ERR_ARG;
+    }
+    pe[l] = 6.626070040e-34 * (299792458.0 * 299792458.0) / 2.0 * (E_stars[l] + E_disk[l]) / n_sent[l];
+    if (lambda_F_lambda) pe[l] = pe[l] * tab_lambda[l] * (double)1.0e-6f;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(d_pe.resize((size_t)M.n_lambda));
+  HIPCHK(hipMemcpyAsync(d_pe, pe.data(), pe.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (J0) {
+    HIPCHK(d_J0.resize(n));
+    HIPCHK(hipMemcpyAsync(d_J0, J0, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // (pe is a local)
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_compute_J(mcgpu_ctx* ctx, const double* n_sent, const double* E_stars, const double* E_disk,
+                               const double* tab_lambda, const double* J0, float* Jio) {
+  int rc = ready(ctx);
+  if (rc) return rc;
+  if (!Jio) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_compute_J: null Jio");
+  const DevModel& M = ctx->M;
+  DevArr<double> d_pe, d_J0;
+  if ((rc = xj_outputs_prepare(ctx, "mcgpu_compute_J", n_sent, E_stars, E_disk, tab_lambda, J0, true, d_pe, d_J0))) return rc;
+  const size_t n = (size_t)M.n_cells * (size_t)M.n_lambda;
+  DevArr<float> d_out;
+  HIPCHK(d_out.resize(n));
+  hipLaunchKernelGGL(k_compute_J, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_xJ_sed.p, J0 ? d_J0.p : nullptr,
+                     d_pe.p, M.volume, M.n_cells, n, d_out.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(Jio, d_out, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_compute_UV_field(mcgpu_ctx* ctx, const double* n_sent, const double* E_stars, const double* E_disk,
+                                      const double* tab_lambda, const double* J0, float* G) {
+  int rc = ready(ctx);
+  if (rc) return rc;
+  if (!G) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_compute_UV_field: null G");
+  const DevModel& M = ctx->M;
+  if (M.n_lambda < 2) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_compute_UV_field: interp needs two wavelengths");
+  DevArr<double> d_pe, d_J0;
+  if ((rc = xj_outputs_prepare(ctx, "mcgpu_compute_UV_field", n_sent, E_stars, E_disk, tab_lambda, J0, false, d_pe, d_J0))) return rc;
+  // wl(:) = span(0.0912, 0.2, n) * 1e-6: span is a running sum in default real (utils.f90:43-62), the product default real too
+  std::vector<double> lamb(M.n_lambda), wl(UV_N);
+  for (int l = 0; l < M.n_lambda; ++l) lamb[l] = tab_lambda[l] * (double)1e-6f;
+  {
+    volatile float dx = (0.2f - 0.0912f) / (float)(UV_N - 1);
+    volatile float sp = 0.0912f;
+    for (int i = 0; i < UV_N; ++i) {
+      if (i > 0) sp = sp + dx;
+      volatile float w = sp * 1e-6f;
+      wl[i] = (double)w;
+    }
+  }
+  const double delta_wl = (wl[UV_N - 1] - wl[0]) / (double)((float)UV_N - 1.0f);
+  DevArr<double> d_lamb, d_wl;
+  DevArr<float> d_G;
+  HIPCHK(d_lamb.resize(lamb.size()));
+  HIPCHK(d_wl.resize(wl.size()));
+  HIPCHK(d_G.resize((size_t)M.n_cells));
+  HIPCHK(hipMemcpyAsync(d_lamb, lamb.data(), lamb.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(d_wl, wl.data(), wl.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_compute_UV, dim3((unsigned)((M.n_cells + 127) / 128)), dim3(128), 0, ctx->stream, ctx->d_xJ_sed.p,
+                     J0 ? d_J0.p : nullptr, d_pe.p, d_lamb.p, d_wl.p, M.volume, M.n_cells, M.n_lambda, delta_wl, d_G.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(G, d_G, (size_t)M.n_cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // (lamb, wl are locals)
+  return MCGPU_OK;
+}
+
 extern "C" int mcgpu_counters_to_accum(mcgpu_ctx* ctx) {
   int rc = ready(ctx);
   if (rc) return rc;
@@ -2482,7 +2685,10 @@ static int launch_mono(mcgpu_ctx* ctx, const MonoArgs& A, int grid_blocks, int b
   // (the commit pass of a context with default-real xI_scatt runs the F32 variant of the deposit code)
   constexpr bool kCommit = !SCOUT;
   const bool f32 = kCommit && A.rt1 && ctx->xI_bytes == 4;
-  if (ctx->voro) fn = kpick_mono_voro(pola, SCOUT, f32);
+  // (... and one that keeps xJ_abs / xN_abs of the SED step the kernels that know that deposit: never a scout pass or a log)
+  const bool xj = kCommit && !log && (A.xJ || A.xN);
+  if (xj) fn = ctx->voro ? kpick_mono_voro_xj(pola, f32) : M.grid_sph ? kpick_mono_sph_xj(l3d, pola, f32) : kpick_mono_xj(l3d, pola, dark, f32);
+  else if (ctx->voro) fn = kpick_mono_voro(pola, SCOUT, f32);
   else if (M.grid_sph) fn = kpick_mono_sph(l3d, pola, SCOUT, f32);
   else fn = kpick_mono(l3d, pola, dark, SCOUT, f32, log);
   // workgroup size: the one that keeps the most wavefronts on a CU, up to 8 (2 per SIMD).  The r02 build needs only
@@ -2532,6 +2738,22 @@ static int launch_mono(mcgpu_ctx* ctx, const MonoArgs& A, int grid_blocks, int b
     if (per_cu_kf > per_cu_max) per_cu_kf = per_cu_max;
     if (per_cu_kf >= per_cu && per_cu_kf > 0) { A2.kf_lds = 1; lds = with_kf; }
   }
+  // The row of xJ_abs (n_cells doubles) in the workgroup's LDS, by the same rule: 2D cylindrical / spherical grids with one
+  // dust class, and only where it does not cost the workgroup its place on the CU ("xj_where" = 2: wherever it fits at
+  // all, else the call is refused; 1: never).
+  A2.xj_lds = 0;
+  if (xj && ctx->opt_xj_where == 2 && !(A.xJ && !l3d && !ctx->voro && !M.n_classes))
+    return fail(ctx, MCGPU_ERR_UNSUPPORTED, "xj_where = 2: the LDS row of xJ_abs is for 2D cylindrical / spherical grids with one dust class and radiation_field_sed bit 0");
+  if (xj && A.xJ && ctx->opt_xj_where != 1 && !l3d && !ctx->voro && !M.n_classes) {
+    const size_t with_xj = mono_lds_bytes(M, A.nRT, threads, pola, slim, lean, A2.kf_lds ? M.n_cells : 0, rowf, M.n_cells);
+    const int per_cu_max = cu_threads / threads > 0 ? cu_threads / threads : 1;
+    int per_cu = (int)((160 * 1024) / lds), per_cu_xj = with_xj <= 160 * 1024 ? (int)((160 * 1024) / with_xj) : 0;
+    if (per_cu > per_cu_max) per_cu = per_cu_max;
+    if (per_cu_xj > per_cu_max) per_cu_xj = per_cu_max;
+    if (ctx->opt_xj_where == 2 ? per_cu_xj > 0 : (per_cu_xj >= per_cu && per_cu_xj > 0)) { A2.xj_lds = 1; lds = with_xj; }
+    else if (ctx->opt_xj_where == 2) return fail(ctx, MCGPU_ERR_UNSUPPORTED, "xj_where = 2: the row of xJ_abs does not fit in the LDS of a workgroup");
+  }
+  if (xj) ctx->last_xj_lds = A2.xj_lds;
   HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int blocks = grid_blocks;
   if (blocks <= 0) {
@@ -3121,6 +3343,16 @@ extern "C" int mcgpu_run_mono(mcgpu_ctx* ctx, const mcgpu_mono_opts* o, double f
   A.flags = tune("MCGPU_DIAG_FLAGS", 0, 0, 255);  // (diagnostic builds only)
   int xlog_mode = xi_log_applicable(ctx, rt1) ? 1 : 0;   // 1: the commit passes log their xI_scatt deposits (mc_xilog.hip.h folds them)
   if (xi_rec_applicable(ctx, rt1)) xlog_mode = 3;        // 3: ... as 16-byte records in the binned log (mc_xirec.hip.h)
+  // xJ_abs / xN_abs of the SED step (option "radiation_field_sed"): this wavelength's rows.  The kernels that log their
+  // deposits do not know this one: the commit passes deposit xI_scatt with atomics.
+  const size_t nrow = (size_t)M.n_cells;
+  if (ctx->opt_radiation_field_sed) {
+    if ((rc = xj_sed_ensure(ctx))) return rc;
+    if (ctx->opt_radiation_field_sed & 1) A.xJ = ctx->d_xJ_sed + nrow * (size_t)(o->lambda - 1);
+    if (ctx->opt_radiation_field_sed & 2) A.xN = ctx->d_xN_sed + nrow * (size_t)(o->lambda - 1);
+    xlog_mode = 0;
+    ctx->last_xj_lds = 0;
+  }
   ctx->xlog_chunks = 0; ctx->xlog_records = 0; ctx->xlog_flights = 0;
   ctx->xrec_chunks = 0; ctx->xrec_buckets = 0; ctx->xrec_split = 0;
   ctx->xrec_records = 0; ctx->xrec_folded = 0; ctx->xrec_overflow = 0; ctx->xrec_drained = 0; ctx->xrec_fold_ms = 0.0;
@@ -3135,6 +3367,10 @@ extern "C" int mcgpu_run_mono(mcgpu_ctx* ctx, const mcgpu_mono_opts* o, double f
   // it every packet is transported twice.  Should a stream reach its count inside the speculative range after all,
   // the accumulators are cleared and the call starts over without speculation (so: only when the call owns them).
   bool speculate = !o->accumulate && ctx->opt_speculation != 0;
+  if (speculate && (A.xJ || A.xN)) {   // (the rows add to what earlier runs of this wavelength left: kept for the restart below)
+    if (A.xJ) { HIPCHK(ctx->d_xJ_keep.reserve(nrow)); HIPCHK(hipMemcpyAsync(ctx->d_xJ_keep, A.xJ, nrow * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream)); }
+    if (A.xN) { HIPCHK(ctx->d_xN_keep.reserve(nrow)); HIPCHK(hipMemcpyAsync(ctx->d_xN_keep, A.xN, nrow * sizeof(unsigned int), hipMemcpyDeviceToDevice, ctx->stream)); }
+  }
 restart:
   std::vector<unsigned long long> need(nc, o->n_photons2), sent(nc, 0ull), start(nc, 0ull);
   std::vector<int> active, done(nc, 0);
@@ -3234,6 +3470,8 @@ restart:
             HIPCHK(hipMemsetAsync(ctx->d_I_spec, 0, (size_t)M.n_cells * ctx->n_phi_I * ctx->n_theta_I * XI_LINE * sizeof(double), ctx->stream));
             HIPCHK(hipMemsetAsync(ctx->d_I_spec_star, 0, (size_t)M.n_cells * sizeof(double), ctx->stream));
           }
+          if (A.xJ) HIPCHK(hipMemcpyAsync(A.xJ, ctx->d_xJ_keep, nrow * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+          if (A.xN) HIPCHK(hipMemcpyAsync(A.xN, ctx->d_xN_keep, nrow * sizeof(unsigned int), hipMemcpyDeviceToDevice, ctx->stream));
           goto restart;
         }
         for (int c = 0; c < nc; ++c) start[c] = cnt[c];   // committed so far: [0, start)
@@ -4871,6 +5109,11 @@ extern "C" int mcgpu_multi_run_mono(mcgpu_multi* mm, const mcgpu_mono_opts* opts
                                     const double* prob_E_cell, uint64_t* n_sent_chunk, double* kernel_ms) {
   if (!mm || !opts) return MCGPU_ERR_ARG;
   const int n = mm->n_dev;
+  for (int i = 0; i < n; ++i)
+    if (mm->ctx[i]->opt_radiation_field_sed) {
+      mm->err = "mcgpu_multi_run_mono: option radiation_field_sed is on: xJ_abs / xN_abs of the SED step are not reduced across contexts";
+      return MCGPU_ERR_UNSUPPORTED;
+    }
   if (opts->n_chunks < n) { mm->err = "mcgpu_multi_run_mono: more devices than streams"; return MCGPU_ERR_ARG; }
   int rc;
   const int what = multi_what(opts);
@@ -4916,6 +5159,11 @@ extern "C" int mcgpu_multi_run_sed(mcgpu_multi* mm, const mcgpu_mono_opts* opts,
                                    double* seconds) {
   if (!mm || !opts || n_wl < 1 || !wl || !Tdust) return MCGPU_ERR_ARG;
   const int n = mm->n_dev;
+  for (int i = 0; i < n; ++i)
+    if (mm->ctx[i]->opt_radiation_field_sed) {
+      mm->err = "mcgpu_multi_run_sed: option radiation_field_sed is on: the rows of xJ_abs / xN_abs of the SED step are not gathered across contexts";
+      return MCGPU_ERR_UNSUPPORTED;
+    }
   if (rt && !tab_RT_az) { mm->err = "mcgpu_multi_run_sed: the ray tracing needs tab_RT_az"; return MCGPU_ERR_ARG; }
   if (opts->accumulate) { mm->err = "mcgpu_multi_run_sed: a wavelength is run once, by one device (accumulate = 0)"; return MCGPU_ERR_ARG; }
   // longest first, each to the device with the least work so far (a wavelength of ref4.1 takes 13 to 370 ms)

@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "mcgpu_set_nlte", "mcgpu_init_reemission_nlte", "mcgpu_set_J0", "mcgpu_temp_finale_nlte", "mcgpu_set_Tdust_1grain",
     "mcgpu_probe_reemission_nlte", "mcgpu_probe_bin_stage", "mcgpu_probe_xi_sort_fold", "mcgpu_probe_xi_commit",
     "mcgpu_probe_math",
+    "mcgpu_reset_radiation_field_sed", "mcgpu_fetch_radiation_field_sed", "mcgpu_compute_J", "mcgpu_compute_UV_field",
 )
 
 
@@ -610,6 +611,53 @@ class Engine:
         self._chk(self.lib.mcgpu_fetch_radiation_field(self.ctx, _p(a, C.c_double) if xN else None,
                                                        _p(b, C.c_double) if xJ else None), "mcgpu_fetch_radiation_field")
         return a, b
+
+    def fetch_radiation_field_sed(self, xJ=True, xN=False):
+        """xJ_abs and xN_abs of the SED step, ``[n_lambda, n_cells]`` each (needs ``set_option("radiation_field_sed",
+        bits)``, bit 0 xJ_abs, bit 1 xN_abs, before ``run_mono``; radiation_field.f90:57-61): ``run_mono(lam, ...)`` adds to
+        row ``lam - 1``."""
+        m = self.model
+        a = np.zeros((m.n_lambda, m.n_cells)) if xJ else None
+        b = np.zeros((m.n_lambda, m.n_cells)) if xN else None
+        self._chk(self.lib.mcgpu_fetch_radiation_field_sed(self.ctx, _p(a, C.c_double) if xJ else None,
+                                                           _p(b, C.c_double) if xN else None), "mcgpu_fetch_radiation_field_sed")
+        return a, b
+
+    def reset_radiation_field_sed(self):
+        """Zeroes xJ_abs and xN_abs of the SED step."""
+        self._chk(self.lib.mcgpu_reset_radiation_field_sed(self.ctx), "mcgpu_reset_radiation_field_sed")
+
+    def _field_inputs(self, n_sent, E_disk, J0):
+        m = self.model
+        ns, ed = _a(n_sent, np.float64), _a(E_disk, np.float64)
+        if ns.shape != (m.n_lambda,) or ed.shape != (m.n_lambda,):
+            raise ValueError("n_sent and E_disk are per wavelength, [n_lambda]")
+        j0 = None
+        if J0 is not None:
+            j0 = _a(J0, np.float64)
+            if j0.shape != (m.n_lambda, m.n_cells):
+                raise ValueError("J0 is [n_lambda, n_cells]")
+        es, lam = _a(m.E_stars, np.float64), _a(m.lam, np.float64)
+        return (_p(ns, C.c_double), _p(es, C.c_double), _p(ed, C.c_double), _p(lam, C.c_double),
+                _p(j0, C.c_double) if j0 is not None else None), (ns, es, ed, lam, j0)   # (the arrays outlive the call)
+
+    def compute_J(self, n_sent, E_disk, J0=None):
+        """``ecriture_J(2)`` on the device (``mcgpu_compute_J``, output.f90:2280-2286): ``J [n_lambda, n_cells]`` in default
+        real, W m^-2 (lambda F_lambda), from the SED step's xJ_abs, the packets sent and E_disk per wavelength."""
+        m = self.model
+        args, keep = self._field_inputs(n_sent, E_disk, J0)
+        out = np.zeros((m.n_lambda, m.n_cells), np.float32)
+        self._chk(self.lib.mcgpu_compute_J(self.ctx, *args, _p(out, C.c_float)), "mcgpu_compute_J")
+        return out
+
+    def compute_UV_field(self, n_sent, E_disk, J0=None):
+        """``compute_UV_field`` on the device (``mcgpu_compute_UV_field``, output.f90:2458-2519): ``G [n_cells]`` in Habing,
+        default real."""
+        m = self.model
+        args, keep = self._field_inputs(n_sent, E_disk, J0)
+        out = np.zeros(m.n_cells, np.float32)
+        self._chk(self.lib.mcgpu_compute_UV_field(self.ctx, *args, _p(out, C.c_float)), "mcgpu_compute_UV_field")
+        return out
 
     def allreduce_device(self, all_reduce):
         """ONE collective per temperature iteration: the counters join the fused accumulator as doubles

@@ -100,7 +100,8 @@ module mcgpu_f
        mcgpu_counters_to_accum, mcgpu_counters_from_accum, mcgpu_temp_approx_diffusion_vertical, mcgpu_set_mrw, mcgpu_set_mrw_exit_spectrum, mcgpu_fetch_radiation_field, &
        mcgpu_build_ksca_CDF, mcgpu_voronoi_tesselation, &
        mcgpu_set_variable_dust, mcgpu_rt1_stars_map_sed, mcgpu_define_dark_zone, mcgpu_init_reemission, mcgpu_init_reemission_ex, mcgpu_repartition_energie, mcgpu_opacity, mcgpu_set_variable_dust_s11, mcgpu_set_scattering_method1, mcgpu_set_rt2, mcgpu_fetch_I_spec, mcgpu_rt1_stars_map_image, mcgpu_set_I_spec, mcgpu_rt2_source, mcgpu_rt2_dust_map, mcgpu_rt2_image, mcgpu_tau_maps, &
-       mcgpu_set_nlte, mcgpu_init_reemission_nlte, mcgpu_set_J0, mcgpu_temp_finale_nlte, mcgpu_set_Tdust_1grain, mcgpu_probe_reemission_nlte
+       mcgpu_set_nlte, mcgpu_init_reemission_nlte, mcgpu_set_J0, mcgpu_temp_finale_nlte, mcgpu_set_Tdust_1grain, mcgpu_probe_reemission_nlte, &
+       mcgpu_reset_radiation_field_sed, mcgpu_fetch_radiation_field_sed, mcgpu_compute_J, mcgpu_compute_UV_field
 
   interface
      integer(c_int) function mcgpu_create(device, ctx) bind(C, name="mcgpu_create")
@@ -306,6 +307,35 @@ module mcgpu_f
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx, xN_abs, xJ_abs
      end function mcgpu_fetch_radiation_field
+
+     ! the SED step's xJ_abs(:,:) / xN_abs(:,:) (radiation_field.f90:57-61; mcgpu_set_option(ctx, "radiation_field_sed", bits),
+     ! bit 0 xJ_abs, bit 1 xN_abs): mcgpu_run_mono of wavelength lambda adds to column lambda
+     integer(c_int) function mcgpu_reset_radiation_field_sed(ctx) bind(C, name="mcgpu_reset_radiation_field_sed")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+     end function mcgpu_reset_radiation_field_sed
+
+     ! (n_cells, n_lambda) each, real(c_double); pass c_null_ptr for either
+     integer(c_int) function mcgpu_fetch_radiation_field_sed(ctx, xJ_abs, xN_abs) bind(C, name="mcgpu_fetch_radiation_field_sed")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, xJ_abs, xN_abs
+     end function mcgpu_fetch_radiation_field_sed
+
+     ! ecriture_J(2)'s Jio(n_cells, n_lambda) (output.f90:2280-2286), default real; J0: c_loc of (n_cells, n_lambda) or c_null_ptr
+     integer(c_int) function mcgpu_compute_J(ctx, n_sent, E_stars, E_disk, tab_lambda, J0, Jio) bind(C, name="mcgpu_compute_J")
+       import :: c_int, c_ptr, c_double, c_float
+       type(c_ptr), value :: ctx, J0
+       real(c_double), intent(in) :: n_sent(*), E_stars(*), E_disk(*), tab_lambda(*)
+       real(c_float), intent(out) :: Jio(*)
+     end function mcgpu_compute_J
+
+     ! compute_UV_field's G(n_cells) in Habing (output.f90:2458-2519), default real
+     integer(c_int) function mcgpu_compute_UV_field(ctx, n_sent, E_stars, E_disk, tab_lambda, J0, G) bind(C, name="mcgpu_compute_UV_field")
+       import :: c_int, c_ptr, c_double, c_float
+       type(c_ptr), value :: ctx, J0
+       real(c_double), intent(in) :: n_sent(*), E_stars(*), E_disk(*), tab_lambda(*)
+       real(c_float), intent(out) :: G(*)
+     end function mcgpu_compute_UV_field
 
      ! modified random walk (module MRW): zeta(:) of initialize_cumulative_zeta, the mean opacities per tab_Temp,
      ! gamma_MRW, the interaction count of dust_transfer.f90:1223, r_lim(0:n_rad); n_zeta = 0 switches it off

@@ -64,6 +64,15 @@ class EngineBackend:
     def dust_map(self, lam, Tdust, res, E_disk):
         return self.e.dust_map_sed(lam, Tdust, res["n_sent"][lam - 1], E_disk)[0]
 
+    def radiation_field_start(self):
+        """The SED step keeps xJ_abs per cell and wavelength (option "radiation_field_sed"), from zero."""
+        self.e.set_option("radiation_field_sed", 1)
+        self.e.reset_radiation_field_sed()
+
+    def radiation_field_outputs(self, n_sent, E_disk):
+        """ecriture_J(2)'s J [n_lambda, n_cells] and compute_UV_field's G [n_cells] from what the wavelength loop left"""
+        return self.e.compute_J(n_sent, E_disk), self.e.compute_UV_field(n_sent, E_disk)
+
     def stars_map(self, lam, star_flux, seed):
         return self.e.stars_map_sed(lam, star_flux, seed=seed)
 
@@ -94,15 +103,20 @@ class EngineBackend:
 
 
 def temperature_and_sed(backend, m, n_thermal, n_photons_lambda, lambdas=None, seed=1, n_chunks=None,
-                        ray_tracing=True, diff_approx=None):
+                        ray_tracing=True, diff_approx=None, radiation_field=False):
     """Returns Tdust, the nine Monte Carlo SED arrays ``sed_mc`` (9, N_phi, N_thet, n_lambda), ``n_sent``
     (packets sent per wavelength in the SED step), ``sed_rt`` (n_lambda, nRT, N_type_flux; dust only) and the
-    wall time of each stage."""
+    wall time of each stage.  ``radiation_field`` (an engine backend): the SED step also keeps its mean radiation field,
+    and ``J`` (n_lambda, n_cells; default real, W m^-2: ``ecriture_J(2)``, output.f90:2280-2286; zero rows for the wavelengths
+    not in ``lambdas``) and ``UV_field`` (n_cells; Habing: ``compute_UV_field``, output.f90:2458-2519, which interpolates
+    over ALL wavelengths: run them all for a meaningful value) are returned too."""
     t = {}
     nlte = backend.nlte_grains() if hasattr(backend, "nlte_grains") else None
     if nlte is not None and ray_tracing:   # (said before anything runs or changes the context)
         raise NotImplementedError("ray-traced SED with grains out of LTE: the ray tracer's thermal emissivity has no per-grain "
                                   "term (dust_ray_tracing.f90:860-890); run with ray_tracing=False")
+    if radiation_field and not hasattr(backend, "radiation_field_start"):
+        raise NotImplementedError("radiation_field=True needs a backend that keeps the SED step's xJ_abs (EngineBackend)")
     t0 = time.perf_counter()
     th = backend.run_thermal(int(n_thermal), seed)
     Tdust = backend.temp_finale(th["E_abs"])
@@ -131,6 +145,8 @@ def temperature_and_sed(backend, m, n_thermal, n_photons_lambda, lambdas=None, s
     sed_rt = np.zeros((nl, rt["RT_n_incl"] * rt["RT_n_az"], rt["N_type_flux"]))
     sed_rt_stars = np.zeros((nl, rt["RT_n_incl"] * rt["RT_n_az"]))
     t["sed_mc"] = t["ray_tracing"] = 0.0
+    if radiation_field:
+        backend.radiation_field_start()
     sed_crossings = 0.0   # cell crossings of the SED step's committed packets, all wavelengths (each one a set of deposits)
     for lam in lambdas:
         if on_device:
@@ -158,6 +174,11 @@ def temperature_and_sed(backend, m, n_thermal, n_photons_lambda, lambdas=None, s
                thermal_counters=th["counters"], E_disk=E_disk, sed_crossings=sed_crossings)
     if Tdust_1grain is not None:
         out["Tdust_1grain"] = Tdust_1grain
+    if radiation_field:
+        # (a wavelength that was not run has a zero row of xJ_abs and no packets: any count but 0 gives its zero row of J)
+        ran = np.zeros(nl, bool)
+        ran[[lam - 1 for lam in lambdas]] = True
+        out["J"], out["UV_field"] = backend.radiation_field_outputs(np.where(ran, n_sent, 1.0), np.asarray(m.extra["E_disk"], float))
     return out
 
 
