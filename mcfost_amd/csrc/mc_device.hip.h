@@ -114,6 +114,16 @@ __device__ __forceinline__ int f64_to_i32_sat(double x) {
   return r;
 #endif
 }
+// x - floor(x) for x >= 0 (or a NaN) as ONE instruction, v_fract_f64 = min(x - floor(x), 1 - 2^-53): on that domain the
+// difference is exact and below 1, so the minimum never applies and the bits are the subtraction's (an integer: +0.0, also
+// beyond 2^52; a NaN: a NaN).  The host emulation writes the subtraction out.
+__device__ __forceinline__ double fract_nonneg(double x) {
+#ifdef MCGPU_LANE_EMULATION
+  return x - floor(x);
+#else
+  return __builtin_amdgcn_fract(x);
+#endif
+}
 // |a - b| + 1 on unsigned integers: one v_sad_u32 (the compiler expands __usad into four instructions here, and has no
 // __builtin_amdgcn_ for it); the host emulation writes the same answer out.
 __device__ __forceinline__ unsigned int sad_plus1_u32(unsigned int a, unsigned int b) {

@@ -646,6 +646,16 @@ __device__ __forceinline__ const RowT& fly_row(const Lds& T, int ri) {
   return *reinterpret_cast<const RowT*>(reinterpret_cast<const char*>(T.row) + __umul24((unsigned int)ri, (unsigned int)sizeof(RowT)));
 #endif
 }
+// The padded key of (ri, zj), pad_key_2d, by a 24-bit multiply-add: the 32-bit form becomes v_mad_u64_u32 on the 32 x 32
+// multiplier, with a carry pair nobody reads.  Both factors are below 2^24 wherever the padded tables exist
+// (upload_cell_opacities, mcgpu.hip, lays them out only for n_rad + 2 and nz + 2 below 2^24; 0 <= zj <= nz + 1).
+__device__ __forceinline__ int fly_key(int n_rad, int ri, int zj) {
+#ifdef MCGPU_LANE_EMULATION
+  return pad_key_2d(n_rad, ri, zj);
+#else
+  return (int)(__umul24((unsigned int)(n_rad + 2), (unsigned int)zj) + (unsigned int)ri);
+#endif
+}
 
 template <bool WALL = false>
 __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, const Flight& p, double& l_out, double& z1_out,
@@ -707,13 +717,18 @@ __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, cons
   double z1 = nd_add(z0, nd_mul(l, w));
   const int ri1 = rad ? ri0 + delta_rad : ri0;
   const double qd = fabs(z1) * (WALL ? fly_row(T, ri1) : T.row[ri1]).rzn;
-  const double fl = floor(qd);
+  // WALL: no floor in front of the conversion.  qd = |z1| rzn is >= 0 or a NaN, and the conversion rounds toward zero: for
+  // 0 <= qd < 2^31 - 1 it gives floor(qd) itself, from 2^31 - 1 on both saturate (floor(qd) >= 2^31 - 1 exactly where qd
+  // is), beyond 2^52 qd is its own floor, and a NaN gives 0 through a floor or without one.  The fraction is v_fract_f64,
+  // min(qd - floor(qd), 1 - 2^-53): for qd >= 0 the difference is exact and below 1, so the minimum never applies; an
+  // integer gives +0.0 and a NaN a NaN both ways (tests/emu/emu_fly_leave.cpp holds both against the floor).
+  const double fl = WALL ? 0.0 : floor(qd);
   // (the minimum on the integers, behind a conversion that saturates: for fl >= 0 the same zj as fly_step_2d's minimum on
   // the doubles; a NaN, which only a broken state brings here, gives zj = 1 where that gives nz + 1)
-  const int fli = f64_to_i32_sat(fl);
+  const int fli = f64_to_i32_sat(WALL ? qd : fl);
   int zjr = (fli < nz ? fli : nz) + 1;
   const bool rad_in = rad && (ri1 >= 1) && (ri1 <= n_rad);
-  const double fr = qd - fl;
+  const double fr = WALL ? fract_nonneg(qd) : qd - fl;
   if (__builtin_expect(rad_in && (fr < 1.0e-4 || fr > 1.0 - 1.0e-4), 0)) {  // (rare)
     const int zq = zj_from_z_real(T, nz, fabs(z1), ri1);
     zjr = zq > nz ? nz + 1 : zq;
@@ -741,13 +756,33 @@ __device__ __forceinline__ int fly_geom_2d(const Lds& T, const DevModel& M, cons
 // (wall ahead, kappa_factor) of the cell they enter -- still one load per crossing, issued one crossing ahead of its use.
 // They hold z1 and w, so they know which wall the next crossing will ask for: away' = (w * z1 > 0.0) is that crossing's
 // own product and compare.  WALL = false is the specification (tests/emu/emu_fly_wall.cpp).
-template <bool DARK, bool LDSE, bool MRW = false, bool VAR = false, bool PAD = false, bool WALL = false>
+//
+// LATE (with WALL): the leave test -- test_exit_grid_cyl and the star's cell -- is not made in front of every crossing but
+// behind the commit of the one crossing that can make it true, and once per visit in front of the loop (fly_leave_2d: the
+// caller runs it for every lane in flight, since a flight also arrives from the FLY ring, after a hand-over or from the
+// last visit in a cell nobody has tested).  A crossing then starts in a tested cell, always.  The lanes that go on hold
+// the cell they enter (ri1, zj1, z1, ic1) and ask a necessary condition of it: ri1 > n_rad (the compare the zj select
+// makes anyway), |z1| > zmaxmax (the top exit needs it whatever zj1 is) or ic1 == star_key.  Behind it, in a rare
+// branch, fly_leave_2d evaluates the specification's whole expression on the committed cell and sets S_EXITED / S_EMIT.
+// That lane's state is the specification's after its NEXT call, which changes nothing but st: position, indices, key,
+// pk_cross, extr and deposits are this crossing's.  (The record of the cell left behind is still loaded: the halo has
+// records.)  The stop and the mirror end the flight; the next flight's pick-up tests its cell.
+// LATE = false is the specification of that form (tests/emu/emu_fly_leave.cpp walks whole flights through both).
+__device__ __forceinline__ void fly_leave_2d(const DevModel& M, Flight& p) {   // PAD: p.ic, p.star_key are padded keys
+  // (bitwise, no short-circuit, as in fly_step_2d; a cell's key is >= 0 and "no star" below 0)
+  const bool out = (p.ri == M.n_rad + 1) | ((p.zj == M.nz + 1) & (fabs(p.z) > M.zmaxmax));
+  const bool killed = (p.ic == p.star_key);
+  if (out | killed) p.st = out ? S_EXITED : S_EMIT;
+}
+
+template <bool DARK, bool LDSE, bool MRW = false, bool VAR = false, bool PAD = false, bool WALL = false, bool LATE = false>
 __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& M, const RunArgs& A, double* E_lds, Flight& p,
                                                   unsigned int& c_dark, const double* kf_pad = nullptr,
                                                   const unsigned char* dark_pad = nullptr, const WallRec* wall = nullptr) {
   static_assert((1.0 + GRID_PREC) - 1.0 == 0x1.68p-47 && 1.0 - (1.0 - GRID_PREC) == 0x1.68p-47, "grid_prec is not 45 ulp");
   static_assert(!PAD || (LDSE && !VAR), "the padded key: LDS deposits, one dust class");
   static_assert(!WALL || PAD, "the wall records are laid out by the padded key");
+  static_assert(!LATE || (WALL && !DARK), "the leave test at the commit: the padded kernels without a dark zone");
   if (p.st == S_FLIGHT) {
     const int n_rad = M.n_rad, nz = M.nz;
     const int ri0 = p.ri, zj0 = p.zj;
@@ -757,7 +792,7 @@ __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& 
     // This rests on the cylindrical grids' encoding, "no star" = -1 (flight_clear, the star's key in the emission); the
     // Voronoi walk's "none" is 0 and has its own test.  PAD: "no star" is -1 - pad_star_bias, below 0 as well)
     const bool killed = PAD ? (p.ic == p.star_key) : (ri0 + (n_rad + 2) * (zj0 + nz + 1) == p.star_key);
-    const bool leave = out | killed;
+    const bool leave = !LATE && (out | killed);   // (LATE: made behind the last commit, or by the caller at pick-up)
     if (__builtin_expect(leave, 0)) {  // (once per packet)
       p.st = out ? S_EXITED : S_EMIT;
     } else {
@@ -786,7 +821,7 @@ __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& 
       } else {
         if (dep) deposit<LDSE>(A.E_abs, E_lds, ic, p.kab * l * p.S0);  // save_radiation_field
         const bool next_real = PAD || (((unsigned)(ri1 - 1) < (unsigned)n_rad) & ((unsigned)(zj1 - 1) < (unsigned)nz));
-        const int ic1 = PAD ? pad_key_2d(n_rad, ri1, zj1)
+        const int ic1 = PAD ? (WALL ? fly_key(n_rad, ri1, zj1) : pad_key_2d(n_rad, ri1, zj1))
                             : (next_real ? (ri1 - 1) + n_rad * (zj1 - 1) : M.n_cells);  // (n_cells: the entry of "no cell", 0)
         if (MRW) p.pk_cross |= 0x80000000u;  // (this flight has left the cell it started in)
         bool mirror = false;
@@ -812,6 +847,11 @@ __device__ __forceinline__ void fly_visit_step_2d(const Lds& T, const DevModel& 
           p.y = __builtin_fma(l, v, y0);
           p.z = z1;
           p.ri = ri1; p.zj = zj1; p.ic = ic1;
+          if (LATE) {
+            // (what a cell that ends the flight must satisfy, see above; bitwise: three compares, one branch)
+            const bool maybe = (ri1 > n_rad) | (fabs(z1) > M.zmaxmax) | (ic1 == p.star_key);
+            if (__builtin_expect(maybe, 0)) fly_leave_2d(M, p);   // (about once per packet)
+          }
         }
       }
     }
@@ -1531,6 +1571,10 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
         // (PAD: the star's cell as a padded key while the lane is in the loop, in place: once per visit, and the records and
         // the code that moves packets between them and the registers keep the one encoding)
         if (PAD) F.star_key -= key_bias;
+        // (WALL: the crossing tests the cell it commits, not the cell it starts in: the cell a flight is picked up in -- from
+        // the FLY ring, after a hand-over, from this wave's last visit -- is tested here, once per visit; a packet killed at
+        // pick-up is counted below like one killed in the loop)
+        if (WALL && F.st == S_FLIGHT) fly_leave_2d(M, F);
 #pragma unroll 1
         for (int it = 0; it < fly_iters; ++it) {
           // back to the rings as soon as enough lanes have nothing to fly (or after fly_iters crossings)
@@ -1547,7 +1591,7 @@ __device__ __forceinline__ void roles_body(const DevModel& M, const RunArgs& A, 
             else finished += fly_step_3d<DARK, LDSE, BIN, VAR, true, MRW>(T, M, A, E_lds, F, c_cross, c_kill, c_dark, dep_ic, dep_v);
             if (BIN) bin_deposit(BS, A.bin, A.E_abs, lane, BP, dep_ic >= 0, dep_ic, dep_v);
           } else {
-            fly_visit_step_2d<DARK, LDSE, MRW, VAR, PAD, WALL>(T, M, A, E_lds, F, c_dark, kf_pad, dark_pad, wall_rec);
+            fly_visit_step_2d<DARK, LDSE, MRW, VAR, PAD, WALL, WALL>(T, M, A, E_lds, F, c_dark, kf_pad, dark_pad, wall_rec);
             if (__popcll(__ballot(F.st != S_FLIGHT)) >= fly_idle) break;  // (the same vote, taken behind the crossing)
           }
         }

@@ -847,7 +847,9 @@ extern "C" int mcgpu_set_stars(mcgpu_ctx* ctx, int n_stars, const double* x, con
 // set, so that either order of the two leaves both halves of a record current.
 static int upload_cell_opacities(mcgpu_ctx* ctx) {
   DevModel& M = ctx->M;
-  const bool pad = !ctx->voro && !M.grid_sph && !M.l3D;
+  // (the flying waves form a padded key by a 24-bit multiply-add, fly_key: no padded tables, hence the plain kernels, for a
+  // grid whose n_rad + 2 or nz + 2 does not fit in 24 bits)
+  const bool pad = !ctx->voro && !M.grid_sph && !M.l3D && M.n_rad + 2 < (1 << 24) && M.nz + 2 < (1 << 24);
   const size_t np = pad ? (size_t)pad_cells_2d(M.n_rad, M.nz) : 0;
   if (pad && ctx->h_wall.size() != np) return fail(ctx, MCGPU_ERR_STATE, "no wall records for this grid");
   int rc;

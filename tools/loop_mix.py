@@ -11,6 +11,10 @@ is counted by kind.  Rare are the blocks that hold the stop's division (v_div_sc
 dominates the loop's latch (a region without a skip branch is part of the straight line): the stop's own deposit and
 commit sit in blocks of their own behind its division, while the deposit of the lanes that go on is in the common path.
 Both sides of a divergent if/else count: a wave runs both.
+A third column, "cold", counts the blocks without a marker that the compiler laid out of line: entered only by a taken
+s_cbranch_execnz and left by s_branch, which is where it puts what __builtin_expect calls unlikely.  In the padded kernels
+without a dark zone that is the leave test behind its guard (fly_leave_2d, about once per packet); the guard itself -- two
+compares, two mask operations and the region's s_and_saveexec -- stays in the common path.
 
 What the counts mean:
   VALU        every v_* instruction (v_readlane / v_writelane included)
@@ -193,11 +197,25 @@ def flying_loop(body, which=0):
     latches = [t for t in loop if h in succ[t]]
     marked = {i for i in loop if any(has(i, mk) for mk in RARE_MARKERS)}
     side = {i for i in marked if not any(i in dom[t] for t in latches)}   # (these take what they dominate with them)
-    common, rare = [], []
+    def last_insn(i):
+        return next((body[k] for k in range(blocks[i][1] - 1, blocks[i][0] - 1, -1) if INSN.match(body[k])), "")
+
+    def out_of_line(i):
+        preds = [p for p in loop if i in succ[p]]
+        name = body[blocks[i][0]].split(":")[0]
+        return bool(preds) and re.match(r"^\s+s_branch\b", last_insn(i)) is not None and \
+            all(re.match(r"^\s+s_cbranch_execnz\s+" + re.escape(name) + r"\s*$", last_insn(p)) for p in preds)
+
+    common, rare, cold = [], [], []
     for i in sorted(loop):
         s, e = blocks[i]
-        (rare if i in marked or any(j in dom[i] for j in side) else common).extend(body[s:e])
-    return common, rare, len(found), body[blocks[h][0]].split(":")[0]
+        if i in marked or any(j in dom[i] for j in side):
+            rare.extend(body[s:e])
+        elif i != h and out_of_line(i):
+            cold.extend(body[s:e])
+        else:
+            common.extend(body[s:e])
+    return common, rare, cold, len(found), body[blocks[h][0]].split(":")[0]
 
 
 def main():
@@ -211,13 +229,13 @@ def main():
     os.makedirs(tmp, exist_ok=True)
     asm = open(compile_asm("kern_roles.hip", tmp)).read().split("\n")
     body, _ = function_text(asm, a.kernel)
-    common, rare, n_loops, header = flying_loop(body, a.loop)
-    cm, rm = mix(common), mix(rare)
+    common, rare, cold, n_loops, header = flying_loop(body, a.loop)
+    cm, rm, km = mix(common), mix(rare), mix(cold)
     print("flying loop of %s\n  (loop %d of %d with an LDS deposit, header %s)" % (a.kernel, a.loop, n_loops, header))
     keys = ["VALU", "FP64", "cndmask", "literal", "SALU", "branches", "regions", "LDS", "VMEM"]
-    print("  %-12s %8s %8s" % ("per iteration", "common", "rare"))
+    print("  %-12s %8s %8s %8s" % ("per iteration", "common", "rare", "cold"))
     for k in keys:
-        print("  %-12s %8d %8d" % (k, cm[k], rm[k]))
+        print("  %-12s %8d %8d %8d" % (k, cm[k], rm[k], km[k]))
     if a.no_regs:
         return
     print("registers (VGPRs incl. AGPRs, scratch bytes per lane):")
