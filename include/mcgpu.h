@@ -646,6 +646,43 @@ int mcgpu_tau_maps(mcgpu_ctx *ctx, const mcgpu_rt_opts *opts, const float *tab_R
                    double map_size, double zoom, double tau_surface, float *tau_map, float *tau_surface_map,
                    double *kernel_ms);
 
+/* Column densities and optical depths to every cell: compute_column (optical_depth.f90:328-415), the routine behind
+ * column_density.fits.gz (write_column_density, output.f90:1440), optical_depth_to_cell.fits.gz (write_optical_depth_to_cell,
+ * :1424) and write_mol_column_density, and the input of the chemistry surrogate (ML_prodimo.f90:187).  From the centre of
+ * every cell four rays -- 1 towards the star at the origin, 2 +z, 3 -z, 4 radially outwards (:368-379) -- each starting in
+ * its own cell and summing l_contrib * factor over the real cells up to the edge of the grid (:385-406):
+ *   type 1  factor = CD_units * gas_density(icell0),                         CD_units = AU_to_m * mu_mH / m_to_cm**2  [g cm^-2]
+ *   type 2  factor = kappa(p_icell, lambda) * kappa_factor(icell0)           (lambda: 1-based; ignored by types 1 and 3)
+ *   type 3  factor = CD_units * gas_density(icell0) * tab_abundance(icell0), CD_units = AU_to_m / m_to_cm**2  [particles cm^-2]
+ * The sums are double, column(n_cells, 4) is a default real, column-major (the reference's array).  All 4 n_cells rays go in
+ * one launch, the cell index fastest.
+ *   r_grid, z_grid, phi_grid [n_cells]  the cells' centres (grid.f90; x = r_grid cos(phi_grid), y = r_grid sin(phi_grid));
+ *                                       NULL on a Voronoi grid, where the FP64 sites of mcgpu_set_grid_voronoi are used
+ *   gas_density [n_cells]               real(dp) (density.f90:27); types 1 and 3
+ *   tab_abundance [n_cells]             default real (molecular_emission.f90:64); type 3
+ *   n_capped (may be NULL)              rays that reached the cap on the number of crossings (below); 0 on a sane grid
+ *   kernel_ms (may be NULL)             device-event time of the launch
+ * No star test, no dark-zone mirror, no random walk and no deposits, like the reference: l_dark_zone does not change the
+ * result.  Every grid (cylindrical, spherical, Voronoi; dust classes).
+ * Departures from the reference.  (1) lvariable_dust: the reference sets p_icell = icell0 before icell0 = next_cell (:386-388)
+ * and so reads the opacity row of the previous cell, and row 0 for the first one; optical_length_tot (:283-287) points at the
+ * current cell, and so does this call.  (2) A centre on the axis (direction 4) or at the origin (direction 1) is a division by
+ * zero in the reference; 0 is written there.  (3) The walk is bounded: a ray stops after 8 (n_rad + 2 nz + n_az) + 64
+ * crossings (Voronoi: 64 ceil(n_cells^(1/3)) + 1024), keeps what it has summed and is counted in n_capped (mc_column.hip.h
+ * gives the reasoning); the reference loops without a bound.
+ * Errors: no grid or opacities MCGPU_ERR_STATE; type, lambda (type 2) or a NULL array that the type needs MCGPU_ERR_ARG.
+ * Nothing is kept in the context, and no option or state of it changes. */
+int mcgpu_compute_column(mcgpu_ctx *ctx, int type, int lambda, const double *r_grid, const double *z_grid,
+                         const double *phi_grid, const double *gas_density, const float *tab_abundance, float *column,
+                         unsigned long long *n_capped, double *kernel_ms);
+
+/* integ_tau (optical_depth.f90:186-244), the two optical depths every run prints and the Phantom coupling asks for before
+ * each temperature step (mcfost2phantom.f90:343): optical_length_tot (:248-324) from the origin along +x (tau_midplane) and
+ * along (sqrt(1 - w0**2), 0, w0), w0 = cos(angle_deg * pi / 180) (tau_angle; angle_deg = angle_interet, a default real).
+ * Default reals; either may be NULL.  The column densities the reference prints next to them (:216-221) are host arithmetic
+ * on dust_mass / volume (mcfost_amd.host.pipeline.integ_tau).  Does not touch the tau_midplane that mcgpu_set_opacity keeps. */
+int mcgpu_integ_tau(mcgpu_ctx *ctx, int lambda, float angle_deg, float *tau_midplane, float *tau_angle);
+
 /* Temp_finale (thermal_emission.f90:870-906): Tdust(icell) from the summed
  * absorbed-energy grid.  E_abs == NULL uses the device accumulator. */
 int mcgpu_temp_finale(mcgpu_ctx *ctx, const double *E_abs, float *Tdust);

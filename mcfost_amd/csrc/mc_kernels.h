@@ -53,6 +53,11 @@ const void* kpick_temp_finale_nlte();
 const void* kpick_init_reemission_nlte();
 const void* kpick_repart_nlte();
 
+// kern_column.hip: column densities and optical depths to every cell (mc_column.hip.h) -- k_compute_column / _voro (one
+// launch: 4 n_cells rays; args DevModel, ColumnArgs[, VoroGrid]), k_integ_tau / _voro (two lanes)
+const void* kpick_compute_column(bool voro, bool l3d);
+const void* kpick_integ_tau(bool voro, bool l3d);
+
 // a run-time bool as a compile-time one: bsel(b, [&](auto B) { ... MCGPU_BV(B) ... })
 template <class F>
 inline const void* bsel(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }

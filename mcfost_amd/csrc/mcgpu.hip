@@ -37,6 +37,7 @@
 #include "mc_stage_probe.hip.h"
 #include "mc_commit_probe.hip.h"
 #include "mc_math_probe.hip.h"
+#include "mc_column_args.h"   // (ColumnArgs, column_cap: the kernels are in kern_column.hip)
 
 using namespace mcgpu;
 
@@ -4378,6 +4379,86 @@ extern "C" int mcgpu_tau_maps(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, const floa
   if (kernel_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1)); *kernel_ms = ms; }
   if (tau_map) HIPCHK(d_tau.get(tau_map, n_pix));
   if (tau_surface_map) HIPCHK(d_surf.get(tau_surface_map, 3 * n_pix));
+  return MCGPU_OK;
+}
+
+// compute_column / integ_tau: see include/mcgpu.h (kernels: mc_column.hip.h, kern_column.hip)
+extern "C" int mcgpu_compute_column(mcgpu_ctx* ctx, int type, int lambda, const double* r_grid, const double* z_grid,
+                                    const double* phi_grid, const double* gas_density, const float* tab_abundance, float* column,
+                                    unsigned long long* n_capped, double* kernel_ms) {
+  int rc = ready(ctx);
+  if (rc) return rc;
+  const DevModel& M = ctx->M;
+  if (type < 1 || type > 3 || !column) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_compute_column: type is 1, 2 or 3");
+  if (type == 2 && (lambda < 1 || lambda > M.n_lambda)) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_compute_column: bad wavelength");
+  if ((type != 2 && !gas_density) || (type == 3 && !tab_abundance))
+    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_compute_column: types 1 and 3 need gas_density, type 3 tab_abundance");
+  if (!ctx->voro && (!r_grid || !z_grid || !phi_grid))
+    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_compute_column: the centres of the cells (r_grid, z_grid, phi_grid)");
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t nc = (size_t)M.n_cells, n_rays = 4 * nc;
+  DevArr<double> d_r, d_z, d_phi, d_gas;
+  DevArr<float> d_ab, d_col;
+  DevArr<unsigned long long> d_cap;
+  if (!ctx->voro) {
+    HIPCHK(d_r.resize(nc)); HIPCHK(d_r.put(r_grid, nc));
+    HIPCHK(d_z.resize(nc)); HIPCHK(d_z.put(z_grid, nc));
+    HIPCHK(d_phi.resize(nc)); HIPCHK(d_phi.put(phi_grid, nc));
+  }
+  if (type != 2) { HIPCHK(d_gas.resize(nc)); HIPCHK(d_gas.put(gas_density, nc)); }
+  if (type == 3) { HIPCHK(d_ab.resize(nc)); HIPCHK(d_ab.put(tab_abundance, nc)); }
+  HIPCHK(d_col.resize(n_rays)); HIPCHK(d_cap.resize(1));
+  HIPCHK(hipMemsetAsync(d_cap.p, 0, sizeof(unsigned long long), ctx->stream));
+  ColumnArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.type = type; A.lambda = type == 2 ? lambda : 1;
+  A.cap = column_cap(M.n_rad, M.nz, M.n_az, M.n_cells, ctx->voro);
+  // CD_units (optical_depth.f90:343-347): AU_to_m and m_to_cm are real(dp), mu_mH = mu * mH a default real (constants.f90:31-35)
+  const float mu_mH = (float)((double)2.3f * (1.007825032231 * (1.0 / 6.022140857e23)));
+  const double AU_to_m = 149597870700.0, m_to_cm2 = 1.0e2 * 1.0e2;
+  A.CD_units = type == 1 ? AU_to_m * (double)mu_mH / m_to_cm2 : AU_to_m / m_to_cm2;
+  A.r_grid = d_r.p; A.z_grid = d_z.p; A.phi_grid = d_phi.p; A.gas_density = d_gas.p; A.abundance = d_ab.p;
+  A.column = d_col.p; A.n_capped = d_cap.p;
+  const size_t lds = lds_bytes(M, true);
+  long blocks = (long)((n_rays + 255) / 256);
+  if (blocks > 65536) blocks = 65536;
+  const void* kern = kpick_compute_column(ctx->voro, M.l3D != 0);
+  HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  DevModel Mv = M;
+  VoroGrid Gv = ctx->V;
+  void* args[] = {&Mv, &A, &Gv};   // (the cylindrical / spherical kernel takes the first two)
+  HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
+  HIPCHK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(256), args, lds, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (kernel_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1)); *kernel_ms = ms; }
+  HIPCHK(d_col.get(column, n_rays));
+  if (n_capped) HIPCHK(d_cap.get(n_capped, 1));
+  return MCGPU_OK;
+}
+
+extern "C" int mcgpu_integ_tau(mcgpu_ctx* ctx, int lambda, float angle_deg, float* tau_midplane, float* tau_angle) {
+  int rc = ready(ctx);
+  if (rc) return rc;
+  const DevModel& M = ctx->M;
+  if (lambda < 1 || lambda > M.n_lambda || (!tau_midplane && !tau_angle)) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_integ_tau: bad argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  DevArr<float> d_out;
+  HIPCHK(d_out.resize(2));
+  const size_t lds = lds_bytes(M, true);
+  const void* kern = kpick_integ_tau(ctx->voro, M.l3D != 0);
+  HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  DevModel Mv = M;
+  VoroGrid Gv = ctx->V;
+  float* out = d_out.p;
+  void* args_cyl[] = {&Mv, &lambda, &angle_deg, &out};
+  void* args_voro[] = {&Mv, &Gv, &lambda, &angle_deg, &out};
+  HIPCHK(hipLaunchKernel(kern, dim3(1), dim3(64), ctx->voro ? args_voro : args_cyl, lds, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float h[2] = {0.0f, 0.0f};
+  HIPCHK(d_out.get(h, 2));
+  if (tau_midplane) *tau_midplane = h[0];
+  if (tau_angle) *tau_angle = h[1];
   return MCGPU_OK;
 }
 

@@ -41,11 +41,16 @@ ABI_SYMBOLS = (
     "mcgpu_probe_reemission_nlte", "mcgpu_probe_bin_stage", "mcgpu_probe_xi_sort_fold", "mcgpu_probe_xi_commit",
     "mcgpu_probe_math",
     "mcgpu_reset_radiation_field_sed", "mcgpu_fetch_radiation_field_sed", "mcgpu_compute_J", "mcgpu_compute_UV_field",
+    "mcgpu_compute_column", "mcgpu_integ_tau",
 )
 
 
 class McgpuError(RuntimeError):
-    pass
+    """``code``: the MCGPU_ERR_* value of the failed call (include/mcgpu.h), or None where no call returned one."""
+
+    def __init__(self, msg="", code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 class RunOpts(C.Structure):
@@ -228,7 +233,7 @@ class Engine:
     def _chk(self, rc, what):
         if rc:
             msg = self.lib.mcgpu_last_error(self.ctx)
-            raise McgpuError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            raise McgpuError(f"{what} failed ({rc}): {msg.decode() if msg else ''}", code=int(rc))
 
     def close(self):
         if getattr(self, "ctx", None) and self.ctx.value:
@@ -935,6 +940,42 @@ class Engine:
             C.c_double(float(map_size)), C.c_double(float(zoom)), C.c_double(float(tau)), _p(tm, C.c_float),
             _p(sm, C.c_float) if surface else None, C.byref(ms)), "mcgpu_tau_maps")
         return tm, sm, ms.value
+
+    def compute_column(self, type, lam=None, gas_density=None, abundance=None):
+        """Column densities (``type`` 1: gas, 3: a molecule with ``abundance``) or the dust optical depth at wavelength
+        ``lam`` (``type`` 2) from every cell's centre towards the star, +z, -z and radially outwards (``mcgpu_compute_column``
+        = ``compute_column``, optical_depth.f90:328-415): ``(column [4, n_cells] float32, n_capped, kernel ms)``; the row of
+        a direction is ``column(:, direction)`` of the reference.  ``n_capped`` counts rays stopped by the cap on crossings:
+        0 on a sane grid."""
+        m = self.model
+        g = m.grid
+        n = m.n_cells
+        d = np.float64
+        if g.get("grid_type", 1) == 3:
+            ctr = [None, None, None]
+        else:
+            ctr = [_a(np.asarray(g[k], d)[:n], d) for k in ("r_grid", "z_grid", "phi_grid")]
+        gas = None if gas_density is None else _a(gas_density, d)
+        ab = None if abundance is None else _a(abundance, np.float32)
+        for a in (gas, ab):
+            if a is not None and a.size != n:
+                raise ValueError("compute_column: gas_density and abundance have one value per cell")
+        col = np.zeros((4, n), np.float32)
+        capped, ms = C.c_ulonglong(), C.c_double()
+        self._chk(self.lib.mcgpu_compute_column(
+            self.ctx, C.c_int(int(type)), C.c_int(int(lam) if lam is not None else 0),
+            *[None if a is None else _p(a, C.c_double) for a in ctr],
+            None if gas is None else _p(gas, C.c_double), None if ab is None else _p(ab, C.c_float),
+            _p(col, C.c_float), C.byref(capped), C.byref(ms)), "mcgpu_compute_column")
+        return col, int(capped.value), ms.value
+
+    def integ_tau(self, lam, angle):
+        """``integ_tau`` (optical_depth.f90:186-244; ``mcgpu_integ_tau``): the optical depths at wavelength ``lam`` from the
+        origin along the midplane (+x) and at ``angle`` degrees from the axis, as default reals."""
+        a, b = C.c_float(), C.c_float()
+        self._chk(self.lib.mcgpu_integ_tau(self.ctx, C.c_int(int(lam)), C.c_float(float(angle)), C.byref(a), C.byref(b)),
+                  "mcgpu_integ_tau")
+        return np.float32(a.value), np.float32(b.value)
 
     def stars_map_image(self, lam, star_flux, npix_x, npix_y, map_size, zoom=1.0, seed=1, ang_disque=0.0,
                         limb_darkening=None):

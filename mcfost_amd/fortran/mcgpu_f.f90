@@ -101,7 +101,8 @@ module mcgpu_f
        mcgpu_build_ksca_CDF, mcgpu_voronoi_tesselation, &
        mcgpu_set_variable_dust, mcgpu_rt1_stars_map_sed, mcgpu_define_dark_zone, mcgpu_init_reemission, mcgpu_init_reemission_ex, mcgpu_repartition_energie, mcgpu_opacity, mcgpu_set_variable_dust_s11, mcgpu_set_scattering_method1, mcgpu_set_rt2, mcgpu_fetch_I_spec, mcgpu_rt1_stars_map_image, mcgpu_set_I_spec, mcgpu_rt2_source, mcgpu_rt2_dust_map, mcgpu_rt2_image, mcgpu_tau_maps, &
        mcgpu_set_nlte, mcgpu_init_reemission_nlte, mcgpu_set_J0, mcgpu_temp_finale_nlte, mcgpu_set_Tdust_1grain, mcgpu_probe_reemission_nlte, &
-       mcgpu_reset_radiation_field_sed, mcgpu_fetch_radiation_field_sed, mcgpu_compute_J, mcgpu_compute_UV_field
+       mcgpu_reset_radiation_field_sed, mcgpu_fetch_radiation_field_sed, mcgpu_compute_J, mcgpu_compute_UV_field, &
+       mcgpu_compute_column, mcgpu_integ_tau
 
   interface
      integer(c_int) function mcgpu_create(device, ctx) bind(C, name="mcgpu_create")
@@ -264,6 +265,30 @@ module mcgpu_f
        real(c_double), value :: map_size, zoom, tau_surface
        type(c_ptr), value :: tau_map, tau_surface_map, kernel_ms
      end function mcgpu_tau_maps
+
+     ! compute_column (optical_depth.f90:328-415) in place of the routine: column(n_cells, 4) as write_column declares it
+     ! (output.f90:1482).  c_loc(r_grid), c_loc(z_grid), c_loc(phi_grid) (grid.f90), or c_null_ptr for all three on a Voronoi
+     ! grid; c_loc(gas_density) (density.f90:27, types 1 and 3) and c_loc(tab_abundance) (molecular_emission.f90:64, type 3) or
+     ! c_null_ptr; n_capped (integer(c_long_long)) and kernel_ms (real(c_double)) by c_loc, or c_null_ptr
+     integer(c_int) function mcgpu_compute_column(ctx, type, lambda, r_grid, z_grid, phi_grid, gas_density, tab_abundance, &
+          column, n_capped, kernel_ms) bind(C, name="mcgpu_compute_column")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: type, lambda
+       type(c_ptr), value :: r_grid, z_grid, phi_grid, gas_density, tab_abundance
+       real(c_float), intent(out) :: column(*)
+       type(c_ptr), value :: n_capped, kernel_ms
+     end function mcgpu_compute_column
+
+     ! integ_tau (optical_depth.f90:186-244): angle_deg = angle_interet; c_loc of two default reals (real(c_float), target),
+     ! or c_null_ptr for one of them
+     integer(c_int) function mcgpu_integ_tau(ctx, lambda, angle_deg, tau_midplane, tau_angle) bind(C, name="mcgpu_integ_tau")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: lambda
+       real(c_float), value :: angle_deg
+       type(c_ptr), value :: tau_midplane, tau_angle
+     end function mcgpu_integ_tau
 
      ! lvariable_dust: p_icell(:) and the tables with the p_n_cells axis, as the modules hold them (mem.f90:213-244)
      ! (the seven scattering tables: c_loc of the arrays, or c_null_ptr for all of them)

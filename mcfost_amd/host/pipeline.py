@@ -101,6 +101,17 @@ class EngineBackend:
     def tau_maps(self, lam, npix_x, npix_y, map_size, zoom, tau, ang_disque):
         return self.e.tau_maps(lam, npix_x, npix_y, map_size, zoom=zoom, tau=tau, ang_disque=ang_disque)[:2]
 
+    # --- disk-structure outputs ---
+    def column(self, type, lam=None, gas_density=None, abundance=None):
+        """compute_column on the device: column [4, n_cells]; a ray stopped by the cap on crossings is an error here"""
+        col, n_capped, _ = self.e.compute_column(type, lam=lam, gas_density=gas_density, abundance=abundance)
+        if n_capped:
+            raise RuntimeError("compute_column: %d rays did not leave the grid within the cap on crossings" % n_capped)
+        return col
+
+    def integ_tau(self, lam, angle):
+        return self.e.integ_tau(lam, angle)
+
 
 def temperature_and_sed(backend, m, n_thermal, n_photons_lambda, lambdas=None, seed=1, n_chunks=None,
                         ray_tracing=True, diff_approx=None, radiation_field=False):
@@ -234,3 +245,43 @@ def image(backend, m, Tdust, lam, n_photons_image, npix_x, npix_y, map_size, zoo
         out["tau_map"], out["tau_surface_map"] = backend.tau_maps(lam, npix_x, npix_y, map_size, zoom, float(tau_surface), ang_disque)
     return out
 
+
+
+def column_maps(backend, m, type, lam=None, gas_density=None, abundance=None):
+    """``write_column``'s array (output.f90:1469-1540): ``compute_column`` (optical_depth.f90:328-415) in the shape the file
+    gets (:1504-1524) -- ``(4, nz, n_rad)`` on a 2D grid, ``(4, n_az, 2 nz, n_rad)`` in 3D, ``(4, n_cells)`` on a Voronoi grid
+    (the FITS axes reversed: C order); index 0 = towards the star, 1 = +z, 2 = -z, 3 = +r.  ``type`` 1: the gas column density
+    (g cm^-2; ``gas_density`` in particles m^-3), 2: the dust optical depth at wavelength ``lam`` (1-based), 3: a molecule's
+    column density (particles cm^-2; ``abundance``)."""
+    col = np.asarray(backend.column(type, lam=lam, gas_density=gas_density, abundance=abundance), np.float32)
+    g = m.grid
+    if g.get("grid_type", 1) == 3:
+        return col.reshape(4, m.n_cells)
+    if g["l3D"]:
+        return col.reshape(4, g["n_az"], 2 * g["nz"], g["n_rad"])
+    return col.reshape(4, g["nz"], g["n_rad"])
+
+
+def integ_tau(backend, m, lam, angle):
+    """``integ_tau`` (optical_depth.f90:186-244): the optical depths at wavelength ``lam`` (1-based) from the origin along the
+    midplane and at ``angle`` degrees from the axis, and next to each the column density (g cm^-2) the reference prints
+    (:216-221, :234-239): tau x the dust density of the first non-empty cell over its opacity.  The densities come from the
+    model's ``dust_mass`` / ``volume`` (or its ``rho_dust``); ``None`` where the model has neither, with variable dust, or
+    where that cell is transparent."""
+    tau_mid, tau_ang = backend.integ_tau(lam, angle)
+    out = dict(tau_midplane=np.float32(tau_mid), tau_angle=np.float32(tau_ang), column_midplane=None, column_angle=None)
+    icell = m.extra.get("icell_ref") if isinstance(getattr(m, "extra", None), dict) else None
+    if icell is None or getattr(m, "variable_dust", None) is not None:
+        return out
+    i = int(icell) - 1
+    if "dust_mass" in m.grid:
+        rho = float(np.asarray(m.grid["dust_mass"], np.float64)[i]) / (float(np.asarray(m.grid["volume"], np.float64)[i]) * M.AU_TO_CM ** 3)
+    elif getattr(m, "rho_dust", None) is not None:
+        rho = float(np.asarray(m.rho_dust, np.float64)[i])      # g cm^-3 = dust_mass / (volume AU_to_cm^3)
+    else:
+        return out
+    opacity = float(m.kappa[lam - 1]) * float(np.asarray(m.kappa_factor, np.float64)[i])
+    if opacity > M.TINY_REAL:
+        out["column_midplane"] = np.float32(float(tau_mid) * rho / (opacity / M.AU_TO_CM))
+        out["column_angle"] = np.float32(float(tau_ang) * rho / (opacity / M.AU_TO_CM))
+    return out
