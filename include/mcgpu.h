@@ -683,6 +683,77 @@ int mcgpu_compute_column(mcgpu_ctx *ctx, int type, int lambda, const double *r_g
  * on dust_mass / volume (mcfost_amd.host.pipeline.integ_tau).  Does not touch the tau_midplane that mcgpu_set_opacity keeps. */
 int mcgpu_integ_tau(mcgpu_ctx *ctx, int lambda, float angle_deg, float *tau_midplane, float *tau_angle);
 
+/* Molecular line channel maps: emission_line_map (mol_transfer.f90:484-687) with intensite_pixel_mol (:691-847), integ_ray_mol
+ * (optical_depth.f90:419-599), local_line_profile (:863-927), phiProf (molecular_emission.f90:183-207) and v_proj (:675-775),
+ * for ONE molecule and every observer direction of mcgpu_set_rt1 at once: replaces the loop over ibin and iaz at
+ * mol_transfer.f90:115-121.  The host supplies the arrays the reference has filled before that loop (level populations, LTE
+ * or not, are already inside kappa_mol_o_freq and emissivite_mol_o_freq).  One ray per pixel centre (n_iter_min = n_iter_max
+ * = 1, :654-655) sent backwards from 10 Rmax through move_to_grid; intersect_stars once at the start, the walk ends at the
+ * star's cell or at test_exit_grid; on a Voronoi grid previous_cell = 0 at every step and one velocity point per cell.  Per
+ * cell n_vpoints = min(max(2, nint(dv / dv_line * 20.)), 200) with dv a default real and the quotient in single precision;
+ * the profile is the mean of norme * exp(-sigma2_m1 (tab_speed - velocity)**2) over the points; opacity, dtau, Snu, I0, I0c,
+ * tau and tau_c follow :521-552 in double; the result is multiplied by (pixelsize / (distance * pc_to_AU))**2 * transfreq.
+ * Arrays are column-major in the reference's layouts; the nTrans axis holds the nTrans_raytracing transitions only (the
+ * caller gathers index_trans_ray_tracing).
+ *   method = 2   pixels: npix_x x npix_y of (map_size/zoom)/max(npix_x,npix_y) AU; with l_sym_ima only i <= npix_x/2 +
+ *                mod(npix_x,2) is computed, the rest stays 0 (:640-644)
+ *   method = 1   the log-sampled spectrum (:576-630): 100 radii x 36 azimuths, rmin_RT = max(0.9 w, 0.05) Rmin, rmax_RT =
+ *                2 Rmax, pixel size fact_A r, l_sym_ima halves cst_phi; summed into spectrum(1,1,...): the pixel axes are 1 x 1
+ * Of opts: ang_disque, Rmax (the distance is lo->distance_pc).
+ * Outputs, default reals, either may be NULL:
+ *   spectrum(npix_x, npix_y, n_speed, nTrans, RT_n_incl, RT_n_az)     continu(npix_x, npix_y, nTrans, RT_n_incl, RT_n_az)
+ *   n_capped (may be NULL)  rays that reached the cap on crossings (departure 5); kernel_ms (may be NULL) device-event time
+ * n_speed * nTrans <= MCGPU_LINE_MAX_CHANNELS: a wave keeps tau and I0 of every channel and transition in LDS.
+ * Departures from the reference.
+ * (1) The CMB term of optical_depth.f90:585-588 is not added: both ways out of the reference's loop are `return`s (:493,
+ *     :496), those lines are never reached, and tab_Cmb_mol is no input.
+ * (2) ldouble_RT is not offered: dtau2 and tau2 are never set at :554-572.
+ * (3) lorigine (origine_mol) is not offered.
+ * (4) The stars' maps that emission_line_map adds at :675-683 are not added: mcgpu_rt1_stars_map_image makes them and the
+ *     host adds them to every channel and to continu.
+ * (5) The walk is bounded as in mcgpu_compute_column (8 (n_rad + 2 nz + n_az) + 64 crossings; Voronoi 64 ceil(n_cells^(1/3))
+ *     + 1024): a capped ray keeps what it has summed and is counted in n_capped.
+ * (6) Method 1 sums its 3600 rays per observer from a buffer in the loop order of :616-628 (radius outer, azimuth inner),
+ *     each addition rounded to a default real as `spectrum = spectrum + IP` is: a second call gives the same bits.  The
+ *     reference's OpenMP order is arbitrary.
+ * (7) Method 1 traces each ray from its sample point center + r sin(phi) x_plan_image + r cos(phi) y_plan_image, which is what
+ *     the comment at :625 intends ("the centre since dx = dy = 0"); the reference passes dx = dy = map_size/zoom and so shifts
+ *     every ray by half a map along both axes.
+ * The dark-zone mirror is not applied (the reference has none here); lsubtract_avg is false (labs is false).
+ * Errors: no grid or opacities, or no mcgpu_set_rt1, MCGPU_ERR_STATE; n_speed * nTrans above the cap, a NULL array that the
+ * mode needs (a Voronoi grid needs vxyz), a method, vfield_mode or vfield_coord out of range, an analytic field that is
+ * neither lkeplerian nor linfall: MCGPU_ERR_ARG.  Nothing is kept in the context, and no option or state of it changes. */
+#define MCGPU_LINE_MAX_CHANNELS 1024
+typedef struct mcgpu_line_opts {
+  int method;                           /* RT_line_method: 1 or 2                                                  */
+  int npix_x, npix_y;                   /* method 2                                                                */
+  double map_size, zoom;                /* method 2; AU                                                            */
+  int l_sym_ima;                        /* mol(imol)%l_sym_ima                                                     */
+  int n_speed;                          /* mol(imol)%n_speed_rt                                                    */
+  const double *tab_speed;              /* tab_speed_rt[n_speed], m/s                                              */
+  int nTrans;                           /* mol(imol)%nTrans_raytracing                                             */
+  const double *transfreq;              /* [nTrans]                                                                */
+  double distance_pc, Rmin;             /* distance (pc); Rmin (AU, method 1)                                      */
+  const double *kappa_mol_o_freq;       /* (n_cells, nTrans)                                                       */
+  const double *emissivite_mol_o_freq;  /* (n_cells, nTrans)                                                       */
+  const double *emissivite_dust;        /* (n_cells, nTrans)                                                       */
+  const double *kappa_abs_LTE;          /* (p_n_cells, nTrans); x the context's kappa_factor, the row of the
+                                           context's dust class of the current cell (optical_depth.f90:524)       */
+  const double *norme_phiProf_m1;       /* [n_cells]                                                               */
+  const double *sigma2_phiProf_m1;      /* [n_cells]                                                               */
+  const float *dv_line;                 /* [n_cells], default real                                                 */
+  int vfield_mode;                      /* 1: analytic (vfield), 2: lvelocity_file (vfield3d); ignored on a Voronoi grid */
+  const float *vfield;                  /* vfield[n_cells] (mode 1) or vfield3d(n_cells, 3) (mode 2), default real */
+  int lkeplerian, linfall;              /* mode 1                                                                  */
+  float chi_infall;                     /* mode 1                                                                  */
+  int vfield_coord;                     /* mode 2: 1 Cartesian, 2 cylindrical, 3 spherical (the sign flips for z < 0
+                                           on 2D grids, molecular_emission.f90:706, :710)                          */
+  const double *vxyz;                   /* Voronoi grids: vxyz(3, n_cells)                                         */
+  int lonly_top, lonly_bottom;
+} mcgpu_line_opts;
+int mcgpu_line_map(mcgpu_ctx *ctx, const mcgpu_rt_opts *opts, const float *tab_RT_az, const mcgpu_line_opts *lo,
+                   float *spectrum, float *continu, unsigned long long *n_capped, double *kernel_ms);
+
 /* Temp_finale (thermal_emission.f90:870-906): Tdust(icell) from the summed
  * absorbed-energy grid.  E_abs == NULL uses the device accumulator. */
 int mcgpu_temp_finale(mcgpu_ctx *ctx, const double *E_abs, float *Tdust);

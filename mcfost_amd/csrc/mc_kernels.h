@@ -58,6 +58,11 @@ const void* kpick_repart_nlte();
 const void* kpick_compute_column(bool voro, bool l3d);
 const void* kpick_integ_tau(bool voro, bool l3d);
 
+// kern_line.hip: molecular line channel maps (mc_line.hip.h) -- k_line_map / _voro (one wave per ray, the lanes are the
+// velocity channels; args DevModel, RtArgs, LineArgs[, VoroGrid]), k_line_sum1 (method 1's sum over the rays; args LineArgs)
+const void* kpick_line_map(bool voro, bool l3d);
+const void* kpick_line_sum1();
+
 // a run-time bool as a compile-time one: bsel(b, [&](auto B) { ... MCGPU_BV(B) ... })
 template <class F>
 inline const void* bsel(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }

@@ -38,6 +38,7 @@
 #include "mc_commit_probe.hip.h"
 #include "mc_math_probe.hip.h"
 #include "mc_column_args.h"   // (ColumnArgs, column_cap: the kernels are in kern_column.hip)
+#include "mc_line_args.h"     // (LineArgs, line_wave_doubles: the kernels are in kern_line.hip)
 
 using namespace mcgpu;
 
@@ -4459,6 +4460,123 @@ extern "C" int mcgpu_integ_tau(mcgpu_ctx* ctx, int lambda, float angle_deg, floa
   HIPCHK(d_out.get(h, 2));
   if (tau_midplane) *tau_midplane = h[0];
   if (tau_angle) *tau_angle = h[1];
+  return MCGPU_OK;
+}
+
+// emission_line_map: see include/mcgpu.h (kernels: mc_line.hip.h, kern_line.hip)
+extern "C" int mcgpu_line_map(mcgpu_ctx* ctx, const mcgpu_rt_opts* o, const float* tab_RT_az, const mcgpu_line_opts* lo,
+                              float* spectrum, float* continu, unsigned long long* n_capped, double* kernel_ms) {
+  int rc = ready(ctx);
+  if (rc) return rc;
+  const DevModel& M = ctx->M;
+  if (!ctx->have_rt1) return fail(ctx, MCGPU_ERR_STATE, "mcgpu_line_map: set the observers first (mcgpu_set_rt1)");
+  if (!o || !tab_RT_az || !lo) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: bad argument");
+  if (lo->method != 1 && lo->method != 2) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: method is 1 or 2");
+  if (lo->n_speed < 1 || lo->nTrans < 1 || (long long)lo->n_speed * lo->nTrans > MCGPU_LINE_MAX_CHANNELS)
+    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: n_speed * nTrans is above MCGPU_LINE_MAX_CHANNELS (or below 1)");
+  if (!lo->tab_speed || !lo->transfreq || !lo->kappa_mol_o_freq || !lo->emissivite_mol_o_freq || !lo->emissivite_dust ||
+      !lo->kappa_abs_LTE || !lo->norme_phiProf_m1 || !lo->sigma2_phiProf_m1)
+    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: a table of the molecule is NULL");
+  if (ctx->voro) {
+    if (!lo->vxyz) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: a Voronoi grid needs vxyz");
+  } else {
+    if (!lo->dv_line || !lo->vfield) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: dv_line and the velocity field");
+    if (lo->vfield_mode == 1) {
+      if (!lo->lkeplerian && !lo->linfall) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: velocity field not defined");
+    } else if (lo->vfield_mode == 2) {
+      if (lo->vfield_coord < 1 || lo->vfield_coord > 3) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: vfield_coord is 1, 2 or 3");
+    } else {
+      return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: vfield_mode is 1 or 2");
+    }
+  }
+  if (lo->method == 2 && (lo->npix_x < 1 || lo->npix_y < 1 || lo->npix_x > 32768 || lo->npix_y > 32768 || !(lo->map_size > 0.0) ||
+                          !(lo->zoom > 0.0)))
+    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: bad image");
+  if (!(o->Rmax > 0.0) || !(lo->distance_pc > 0.0) || (lo->method == 1 && !(lo->Rmin > 0.0)))
+    return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: Rmax, distance_pc (and Rmin for method 1) must be positive");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int nRT = ctx->RT_n_incl * ctx->RT_n_az, nT = lo->nTrans, ns = lo->n_speed;
+  const size_t nc = (size_t)M.n_cells, pnc = M.n_classes ? (size_t)M.n_classes : 1;
+  const int npx = lo->method == 2 ? lo->npix_x : 1, npy = lo->method == 2 ? lo->npix_y : 1;
+  const size_t n_cont = (size_t)npx * npy * nT * nRT, n_spec = n_cont * ns;
+  DevArr<float> d_az, d_spec, d_cont, d_dv, d_vf;
+  DevArr<double> d_speed, d_freq, d_kmol, d_emol, d_edust, d_kabs, d_norme, d_s2, d_vxyz, d_rays;
+  DevArr<unsigned long long> d_cap;
+  HIPCHK(d_az.resize(ctx->RT_n_az)); HIPCHK(d_az.put(tab_RT_az, ctx->RT_n_az));
+  HIPCHK(d_speed.resize(ns)); HIPCHK(d_speed.put(lo->tab_speed, ns));
+  HIPCHK(d_freq.resize(nT)); HIPCHK(d_freq.put(lo->transfreq, nT));
+  HIPCHK(d_kmol.resize(nc * nT)); HIPCHK(d_kmol.put(lo->kappa_mol_o_freq, nc * nT));
+  HIPCHK(d_emol.resize(nc * nT)); HIPCHK(d_emol.put(lo->emissivite_mol_o_freq, nc * nT));
+  HIPCHK(d_edust.resize(nc * nT)); HIPCHK(d_edust.put(lo->emissivite_dust, nc * nT));
+  HIPCHK(d_kabs.resize(pnc * nT)); HIPCHK(d_kabs.put(lo->kappa_abs_LTE, pnc * nT));
+  HIPCHK(d_norme.resize(nc)); HIPCHK(d_norme.put(lo->norme_phiProf_m1, nc));
+  HIPCHK(d_s2.resize(nc)); HIPCHK(d_s2.put(lo->sigma2_phiProf_m1, nc));
+  if (ctx->voro) {
+    HIPCHK(d_vxyz.resize(3 * nc)); HIPCHK(d_vxyz.put(lo->vxyz, 3 * nc));
+  } else {
+    const size_t nv = lo->vfield_mode == 2 ? 3 * nc : nc;
+    HIPCHK(d_dv.resize(nc)); HIPCHK(d_dv.put(lo->dv_line, nc));
+    HIPCHK(d_vf.resize(nv)); HIPCHK(d_vf.put(lo->vfield, nv));
+  }
+  if (spectrum) { HIPCHK(d_spec.resize(n_spec)); HIPCHK(hipMemsetAsync(d_spec.p, 0, n_spec * sizeof(float), ctx->stream)); }
+  if (continu) { HIPCHK(d_cont.resize(n_cont)); HIPCHK(hipMemsetAsync(d_cont.p, 0, n_cont * sizeof(float), ctx->stream)); }
+  HIPCHK(d_cap.resize(1));
+  HIPCHK(hipMemsetAsync(d_cap.p, 0, sizeof(unsigned long long), ctx->stream));
+  RtArgs R;
+  std::memset(&R, 0, sizeof(R));
+  R.RT_n_incl = ctx->RT_n_incl; R.nRT = nRT; R.ang_disque = o->ang_disque;
+  R.rt_u = ctx->d_rt_u; R.rt_v = ctx->d_rt_v; R.rt_w = ctx->d_rt_w; R.rt_az = d_az.p;
+  LineArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.method = lo->method; A.nRT = nRT;
+  A.npix_x = npx; A.npix_y = npy;
+  A.npix_x_max = (lo->method == 2 && lo->l_sym_ima) ? npx / 2 + npx % 2 : npx;                  // (:640-644)
+  A.map_size = lo->map_size;
+  A.taille_pix = lo->method == 2 ? (lo->map_size / lo->zoom) / (double)(npx > npy ? npx : npy) : 0.0;   // (:636)
+  A.l_far = 10.0 * o->Rmax;                                                                      // (:566)
+  A.Rmin = lo->Rmin; A.Rmax = o->Rmax;
+  A.cst_phi = (lo->l_sym_ima ? M_PI : 2.0 * M_PI) / (double)LINE_N_PHI_RT;                       // (:609-613)
+  const double pc_to_AU = 648000.0 / M_PI;
+  A.inv_dist = 1.0 / (lo->distance_pc * pc_to_AU);
+  A.n_speed = ns; A.nTrans = nT;
+  A.tab_speed = d_speed.p; A.transfreq = d_freq.p; A.kappa_mol = d_kmol.p; A.emis_mol = d_emol.p; A.emis_dust = d_edust.p;
+  A.kabs_LTE = d_kabs.p; A.p_n_cells = (int)pnc; A.norme_m1 = d_norme.p; A.sigma2_m1 = d_s2.p; A.dv_line = d_dv.p;
+  A.vfield_mode = lo->vfield_mode; A.lkeplerian = lo->lkeplerian; A.linfall = lo->linfall; A.vfield_coord = lo->vfield_coord;
+  A.chi_infall = lo->chi_infall; A.vfield = d_vf.p; A.vxyz = d_vxyz.p;
+  A.lonly_top = lo->lonly_top; A.lonly_bottom = lo->lonly_bottom;
+  A.cap = column_cap(M.n_rad, M.nz, M.n_az, M.n_cells, ctx->voro);
+  A.spectrum = d_spec.p; A.continu = d_cont.p; A.n_capped = d_cap.p;
+  const long n_rays = lo->method == 2 ? (long)nRT * A.npix_x_max * npy : (long)nRT * LINE_N_RAD_RT * LINE_N_PHI_RT;
+  if (lo->method == 1) {
+    HIPCHK(d_rays.resize((size_t)n_rays * nT * (ns + 1)));
+    A.rays = d_rays.p;
+  }
+  // one wave per ray, up to 4 waves in a workgroup: as many as the tables and the waves' shares of the LDS allow
+  const size_t lds_tab = (lds_bytes(M, true) + 7) / 8 * 8, lds_wave = line_wave_doubles(ns, nT) * sizeof(double);
+  int waves = 4;
+  while (waves > 1 && lds_tab + waves * lds_wave > 160 * 1024) --waves;
+  const size_t lds = lds_tab + waves * lds_wave;
+  if (lds > 160 * 1024) return fail(ctx, MCGPU_ERR_ARG, "mcgpu_line_map: the grid's tables and one wave's channels exceed the LDS");
+  long blocks = (n_rays + waves - 1) / waves;
+  if (blocks > 65536) blocks = 65536;
+  const void* kern = kpick_line_map(ctx->voro, M.l3D != 0);
+  HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  DevModel Mv = M;
+  VoroGrid Gv = ctx->V;
+  void* args[] = {&Mv, &R, &A, &Gv};   // (the cylindrical / spherical kernel takes the first three)
+  HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
+  HIPCHK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(64 * waves), args, lds, ctx->stream));
+  if (lo->method == 1) {
+    const long n_val = (long)nRT * nT * (ns + 1);
+    void* sargs[] = {&A};
+    HIPCHK(hipLaunchKernel(kpick_line_sum1(), dim3((unsigned)((n_val + 255) / 256)), dim3(256), sargs, 0, ctx->stream));
+  }
+  HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (kernel_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1)); *kernel_ms = ms; }
+  if (spectrum) HIPCHK(d_spec.get(spectrum, n_spec));
+  if (continu) HIPCHK(d_cont.get(continu, n_cont));
+  if (n_capped) HIPCHK(d_cap.get(n_capped, 1));
   return MCGPU_OK;
 }
 

@@ -41,7 +41,7 @@ ABI_SYMBOLS = (
     "mcgpu_probe_reemission_nlte", "mcgpu_probe_bin_stage", "mcgpu_probe_xi_sort_fold", "mcgpu_probe_xi_commit",
     "mcgpu_probe_math",
     "mcgpu_reset_radiation_field_sed", "mcgpu_fetch_radiation_field_sed", "mcgpu_compute_J", "mcgpu_compute_UV_field",
-    "mcgpu_compute_column", "mcgpu_integ_tau",
+    "mcgpu_compute_column", "mcgpu_integ_tau", "mcgpu_line_map",
 )
 
 
@@ -83,6 +83,58 @@ class RtOpts(C.Structure):
     _fields_ = [("lambda_", C.c_int), ("wl_um", C.c_double), ("E_src", C.c_double), ("n_sent_photons", C.c_double),
                 ("distance", C.c_double), ("ang_disque", C.c_double), ("l_sym_ima", C.c_int),
                 ("tau_dark_zone_obs", C.c_double), ("Rmin", C.c_double), ("Rmax", C.c_double)]
+
+
+class LineOpts(C.Structure):           # mcgpu_line_opts
+    _dp, _fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+    _fields_ = [("method", C.c_int), ("npix_x", C.c_int), ("npix_y", C.c_int), ("map_size", C.c_double), ("zoom", C.c_double),
+                ("l_sym_ima", C.c_int), ("n_speed", C.c_int), ("tab_speed", _dp), ("nTrans", C.c_int), ("transfreq", _dp),
+                ("distance_pc", C.c_double), ("Rmin", C.c_double), ("kappa_mol_o_freq", _dp), ("emissivite_mol_o_freq", _dp),
+                ("emissivite_dust", _dp), ("kappa_abs_LTE", _dp), ("norme_phiProf_m1", _dp), ("sigma2_phiProf_m1", _dp),
+                ("dv_line", _fp), ("vfield_mode", C.c_int), ("vfield", _fp), ("lkeplerian", C.c_int), ("linfall", C.c_int),
+                ("chi_infall", C.c_float), ("vfield_coord", C.c_int), ("vxyz", _dp), ("lonly_top", C.c_int),
+                ("lonly_bottom", C.c_int)]
+
+
+def line_opts(mol, n_cells, p_n_cells, distance_pc, Rmin, method=2, npix_x=1, npix_y=1, map_size=1.0, zoom=1.0, l_sym_ima=False,
+              lonly_top=False, lonly_bottom=False):
+    """(LineOpts, the arrays it points at) from a molecule's tables ``mol`` (mcfost_amd.host.molecule.line_tables): arrays
+    ``[nTrans, n_cells]`` in C order are the reference's ``(n_cells, nTrans)``.  An entry that is None stays NULL.  Sizes are
+    checked here, because the library reads n_cells values behind every pointer."""
+    d, f = np.float64, np.float32
+    ts, fr = _a(mol["tab_speed"], d).reshape(-1), _a(mol["transfreq"], d).reshape(-1)
+    nT = fr.size
+    keep = dict(tab_speed=ts, transfreq=fr)
+
+    def arr(key, dt, size):
+        a = mol.get(key)
+        if a is None:
+            return None
+        a = _a(a, dt)
+        if a.size != size:
+            raise ValueError("line_map: %s holds %d values, not %d" % (key, a.size, size))
+        keep[key] = a
+        return a
+
+    for k in ("kappa_mol_o_freq", "emissivite_mol_o_freq", "emissivite_dust"):
+        arr(k, d, nT * n_cells)
+    arr("kappa_abs_LTE", d, nT * p_n_cells)
+    arr("norme_phiProf_m1", d, n_cells)
+    arr("sigma2_phiProf_m1", d, n_cells)
+    arr("dv_line", f, n_cells)
+    mode = int(mol.get("vfield_mode", 1))
+    arr("vfield", f, 3 * n_cells if mode == 2 else n_cells)
+    arr("vxyz", d, 3 * n_cells)
+    o = LineOpts()
+    o.method, o.npix_x, o.npix_y, o.map_size, o.zoom = int(method), int(npix_x), int(npix_y), float(map_size), float(zoom)
+    o.l_sym_ima, o.n_speed, o.nTrans = int(bool(l_sym_ima)), ts.size, nT
+    o.distance_pc, o.Rmin = float(distance_pc), float(Rmin)
+    o.vfield_mode, o.lkeplerian, o.linfall = mode, int(bool(mol.get("lkeplerian", False))), int(bool(mol.get("linfall", False)))
+    o.chi_infall, o.vfield_coord = float(mol.get("chi_infall", 1.0)), int(mol.get("vfield_coord", 1))
+    o.lonly_top, o.lonly_bottom = int(bool(lonly_top)), int(bool(lonly_bottom))
+    for k, a in keep.items():
+        setattr(o, k, _p(a, C.c_float if a.dtype == np.float32 else C.c_double))
+    return o, keep
 
 
 class SedWavelength(C.Structure):
@@ -968,6 +1020,36 @@ class Engine:
             None if gas is None else _p(gas, C.c_double), None if ab is None else _p(ab, C.c_float),
             _p(col, C.c_float), C.byref(capped), C.byref(ms)), "mcgpu_compute_column")
         return col, int(capped.value), ms.value
+
+    def line_map(self, mol, method=2, npix_x=1, npix_y=1, map_size=None, zoom=1.0, ang_disque=0.0, l_sym_ima=False,
+                 lonly_top=False, lonly_bottom=False, spectrum=True, continu=True):
+        """A molecule's channel maps for every observer direction (``mcgpu_line_map`` = ``emission_line_map``,
+        mol_transfer.f90:484-847): ``(spectrum [nRT, nTrans, n_speed, npix_y, npix_x], continu [nRT, nTrans, npix_y, npix_x],
+        n_capped, kernel ms)`` as float32, either None when not asked for.  ``mol``: the tables of
+        ``mcfost_amd.host.molecule.line_tables``.  ``method`` 1 is the log-sampled spectrum: the pixel axes are 1 x 1."""
+        m = self.model
+        rt = m.rt
+        if not getattr(self, "_rt1", False):
+            self.set_rt1()
+        if method == 1:
+            npix_x = npix_y = 1
+        if map_size is None:
+            map_size = 2.0 * float(m.cfg.rout)
+        vd = getattr(m, "variable_dust", None)
+        lo, keep = line_opts(mol, m.n_cells, int(vd["p_n_cells"]) if vd is not None else 1, float(m.cfg.distance),
+                             float(m.cfg.rin), method, npix_x, npix_y, map_size, zoom, l_sym_ima, lonly_top, lonly_bottom)
+        o = RtOpts(1, float(m.lam[0]), 1.0, 1.0, float(m.cfg.distance), float(ang_disque), int(bool(l_sym_ima)), 100.0,
+                   float(m.cfg.rin), float(m.cfg.rout))
+        nRT = rt["RT_n_incl"] * rt["RT_n_az"]
+        spec = np.zeros((nRT, lo.nTrans, lo.n_speed, npix_y, npix_x), np.float32) if spectrum else None
+        cont = np.zeros((nRT, lo.nTrans, npix_y, npix_x), np.float32) if continu else None
+        capped, ms = C.c_ulonglong(), C.c_double()
+        self._chk(self.lib.mcgpu_line_map(
+            self.ctx, C.byref(o), _p(_a(rt["tab_RT_az"], np.float32), C.c_float), C.byref(lo),
+            None if spec is None else _p(spec, C.c_float), None if cont is None else _p(cont, C.c_float),
+            C.byref(capped), C.byref(ms)), "mcgpu_line_map")
+        del keep
+        return spec, cont, int(capped.value), ms.value
 
     def integ_tau(self, lam, angle):
         """``integ_tau`` (optical_depth.f90:186-244; ``mcgpu_integ_tau``): the optical depths at wavelength ``lam`` from the

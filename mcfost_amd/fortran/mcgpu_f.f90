@@ -65,6 +65,30 @@ module mcgpu_f
      real(c_double) :: Rmin, Rmax
   end type mcgpu_rt_opts
 
+  ! molecular line channel maps (include/mcgpu.h: mcgpu_line_opts); every array by c_loc, c_null_ptr where the mode does not
+  ! read it
+  type, bind(C), public :: mcgpu_line_opts
+     integer(c_int) :: method              ! RT_line_method
+     integer(c_int) :: npix_x, npix_y
+     real(c_double) :: map_size, zoom
+     integer(c_int) :: l_sym_ima           ! mol(imol)%l_sym_ima
+     integer(c_int) :: n_speed             ! mol(imol)%n_speed_rt
+     type(c_ptr)    :: tab_speed           ! tab_speed_rt(n_speed)
+     integer(c_int) :: nTrans              ! mol(imol)%nTrans_raytracing
+     type(c_ptr)    :: transfreq           ! transfreq(index_trans_ray_tracing(1:nTrans))
+     real(c_double) :: distance_pc, Rmin
+     type(c_ptr)    :: kappa_mol_o_freq, emissivite_mol_o_freq, emissivite_dust   ! (n_cells, nTrans), gathered
+     type(c_ptr)    :: kappa_abs_LTE       ! (p_n_cells, nTrans), gathered
+     type(c_ptr)    :: norme_phiProf_m1, sigma2_phiProf_m1, dv_line
+     integer(c_int) :: vfield_mode         ! 1: vfield, 2: vfield3d (lvelocity_file)
+     type(c_ptr)    :: vfield
+     integer(c_int) :: lkeplerian, linfall
+     real(c_float)  :: chi_infall
+     integer(c_int) :: vfield_coord
+     type(c_ptr)    :: vxyz                ! Voronoi grids: (3, n_cells)
+     integer(c_int) :: lonly_top, lonly_bottom
+  end type mcgpu_line_opts
+
   ! one wavelength of mcgpu_multi_run_sed (include/mcgpu.h: mcgpu_sed_wavelength)
   type, bind(C), public :: mcgpu_sed_wavelength
      integer(c_int) :: lambda, p_lambda
@@ -102,7 +126,7 @@ module mcgpu_f
        mcgpu_set_variable_dust, mcgpu_rt1_stars_map_sed, mcgpu_define_dark_zone, mcgpu_init_reemission, mcgpu_init_reemission_ex, mcgpu_repartition_energie, mcgpu_opacity, mcgpu_set_variable_dust_s11, mcgpu_set_scattering_method1, mcgpu_set_rt2, mcgpu_fetch_I_spec, mcgpu_rt1_stars_map_image, mcgpu_set_I_spec, mcgpu_rt2_source, mcgpu_rt2_dust_map, mcgpu_rt2_image, mcgpu_tau_maps, &
        mcgpu_set_nlte, mcgpu_init_reemission_nlte, mcgpu_set_J0, mcgpu_temp_finale_nlte, mcgpu_set_Tdust_1grain, mcgpu_probe_reemission_nlte, &
        mcgpu_reset_radiation_field_sed, mcgpu_fetch_radiation_field_sed, mcgpu_compute_J, mcgpu_compute_UV_field, &
-       mcgpu_compute_column, mcgpu_integ_tau
+       mcgpu_compute_column, mcgpu_integ_tau, mcgpu_line_map
 
   interface
      integer(c_int) function mcgpu_create(device, ctx) bind(C, name="mcgpu_create")
@@ -289,6 +313,19 @@ module mcgpu_f
        real(c_float), value :: angle_deg
        type(c_ptr), value :: tau_midplane, tau_angle
      end function mcgpu_integ_tau
+
+     ! emission_line_map for one molecule and every observer direction (mol_transfer.f90:115-121): spectrum(:,:,:,:,:,:) and
+     ! continu(:,:,:,:,:) of module molecular_emission by c_loc, or c_null_ptr; n_capped (integer(c_long_long)) and kernel_ms
+     ! (real(c_double)) by c_loc, or c_null_ptr.  The stars' maps are added by the host (INTEGRATION.md)
+     integer(c_int) function mcgpu_line_map(ctx, opts, tab_RT_az, lo, spectrum, continu, n_capped, kernel_ms) &
+          bind(C, name="mcgpu_line_map")
+       import :: c_int, c_ptr, c_float, mcgpu_rt_opts, mcgpu_line_opts
+       type(c_ptr), value :: ctx
+       type(mcgpu_rt_opts), intent(in) :: opts
+       real(c_float), intent(in) :: tab_RT_az(*)
+       type(mcgpu_line_opts), intent(in) :: lo
+       type(c_ptr), value :: spectrum, continu, n_capped, kernel_ms
+     end function mcgpu_line_map
 
      ! lvariable_dust: p_icell(:) and the tables with the p_n_cells axis, as the modules hold them (mem.f90:213-244)
      ! (the seven scattering tables: c_loc of the arrays, or c_null_ptr for all of them)

@@ -112,6 +112,14 @@ class EngineBackend:
     def integ_tau(self, lam, angle):
         return self.e.integ_tau(lam, angle)
 
+    # --- molecular lines ---
+    def line_map(self, mol, **kw):
+        """emission_line_map on the device: (spectrum, continu); a ray stopped by the cap on crossings is an error here"""
+        spec, cont, n_capped, _ = self.e.line_map(mol, **kw)
+        if n_capped:
+            raise RuntimeError("line_map: %d rays did not leave the grid within the cap on crossings" % n_capped)
+        return spec, cont
+
 
 def temperature_and_sed(backend, m, n_thermal, n_photons_lambda, lambdas=None, seed=1, n_chunks=None,
                         ray_tracing=True, diff_approx=None, radiation_field=False):
@@ -260,6 +268,22 @@ def column_maps(backend, m, type, lam=None, gas_density=None, abundance=None):
     if g["l3D"]:
         return col.reshape(4, g["n_az"], 2 * g["nz"], g["n_rad"])
     return col.reshape(4, g["nz"], g["n_rad"])
+
+
+def line_map(backend, m, mol, method=2, npix_x=1, npix_y=1, map_size=None, zoom=1.0, ang_disque=0.0, l_sym_ima=False,
+             lonly_top=False, lonly_bottom=False):
+    """A molecule's line cube and continuum (``emission_line_map``, mol_transfer.f90:484-687, without the stars' maps) in the
+    shapes of the files (``ecriture_spectre``: lines.fits.gz and its continuum extension, FITS axes reversed: C order):
+    ``spectrum (RT_n_az, RT_n_incl, nTrans, n_speed, npix_y, npix_x)`` and ``continu (RT_n_az, RT_n_incl, nTrans, npix_y,
+    npix_x)``, default reals.  ``mol``: ``mcfost_amd.host.molecule.line_tables``.  ``method`` 1: the pixel axes are 1 x 1."""
+    if method == 1:
+        npix_x = npix_y = 1
+    spec, cont = backend.line_map(mol, method=method, npix_x=npix_x, npix_y=npix_y, map_size=map_size, zoom=zoom,
+                                  ang_disque=ang_disque, l_sym_ima=l_sym_ima, lonly_top=lonly_top, lonly_bottom=lonly_bottom)
+    n_incl, n_az = m.rt["RT_n_incl"], m.rt["RT_n_az"]
+    nT, ns = np.asarray(mol["transfreq"]).size, np.asarray(mol["tab_speed"]).size
+    return (np.asarray(spec, np.float32).reshape(n_az, n_incl, nT, ns, npix_y, npix_x),
+            np.asarray(cont, np.float32).reshape(n_az, n_incl, nT, npix_y, npix_x))
 
 
 def integ_tau(backend, m, lam, angle):
